@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""bench.py -- bee2 hot path on MI355X: bashF perms/s (headline), beltCTR GiB/s, bign-curve256v1 verifies/s,
+"""bench.py -- bee2 hot path on MI355X: bashF perms/s (headline); with --full also beltCTR GiB/s, bign-curve256v1 verifies/s,
 bash512+beltMAC messages/s (BASELINE.json configs[1..4]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--all | --only a,b,...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--all | --only a,b,...]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU.  A "step" is one pass of the hot path over one batch of synthetic input already resident in HBM: the
@@ -10,15 +10,21 @@ headline step is bashF over 2^20 independent 192-byte states.  Batches are indep
 collective ("weak" scaling: per-GPU work fixed); RCCL carries the one parameter broadcast (key / ctr0, 48 bytes) and the
 max-over-ranks of each timed region.
 
+A plain run does only what the headline figure needs: set-up, warm-up, exactly K timed bashF steps, the outputs of the last step
+(--dump-outputs) and the result line, whose roofline figures are those of the timed launches themselves.  --dump-outputs DIR writes
+DIR/bashF_states.npy: a fixed, seeded sample of 2^16 of the 2^20 states the last timed step left, as float64 rows of 48 little-endian
+32-bit words (exact); the input is the seeded synthetic batch, so equal arguments give equal outputs.
+
 Output (bench_legs/line.py): one figure per line for a reader, then -- LAST line of stdout, rank 0 -- ONE strict-JSON line of at
 most 8000 characters: the contract's fields, `roofline` (24 flat scalars: the headline kernel's algorithmic bytes / hipEvent
 launch time against the HBM peak, the other three BASELINE metrics with their fractions, the fixed-N (strong) split of SURVEY 8e
 as strong_pred_8_* at N = 1 / strong_speedup_* at N > 1, ranks / devices seen; `traffic` = the PMC HBM bytes of the headline launch,
 taken in this very run by re-running that leg under rocprofv3 --pmc, bench_legs/pmc_live.py) and `cpu_baseline` (the reference itself,
-oracle/_ref, on this box's host cores; rank 0, N = 1).  Every leg's full record goes to gpurun_out/bench_detail.json.
+oracle/_ref, on this machine's host cores; rank 0, N = 1).  With --full every leg's record goes to a side file named by the line's `detail`.
 
-Default: the four BASELINE legs.  --all adds the SURVEY 8f legs (signing, bulk modes, ragged hashes, belt-dwp, the wider curves,
-key validation / key-table verification, single-call latency); --only picks legs by name.  The legs live in bench_legs/.
+--full: the four BASELINE legs with their strong splits, sweeps, host-pointer rates, shader clock, live PMC and cpu_baseline.
+--all (implies --full) adds the SURVEY 8f legs (signing, bulk modes, ragged hashes, belt-dwp, the wider curves, key validation /
+key-table verification, single-call latency); --only picks legs by name.  The legs live in bench_legs/.
 """
 import argparse
 import json
@@ -60,15 +66,26 @@ def parse(argv=None):
     ap.add_argument("--no-live-pmc", action="store_true",
                     help="do not re-run the headline leg under rocprofv3 --pmc for `roofline.traffic` (then the committed profile of the "
                          "same launch is replayed, or null)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the other BASELINE legs, strong splits, sweeps, host-pointer rates, shader clock, "
+                         "live PMC and cpu_baseline (a plain run times the bashF headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last bashF step computed to DIR/bashF_states.npy (a seeded 2^16-state "
+                         "sample, float64 32-bit words)")
     ap.add_argument("--launch-selftest", action="store_true",
                     help="ranks only form the process group, reduce one number and rank 0 prints the line's launch fields "
                          "(no GPU work; tests/test_bench_launch.py runs this on CPU with BEE2_BENCH_BACKEND=gloo)")
     args = ap.parse_args(argv)
+    args.full = args.full or args.all
+    if not args.full:                      # plain run: the headline's own launches and nothing else
+        args.headline_only = args.no_cpu = args.no_live_pmc = True
     if not args.only:
-        args.only = ",".join(WORKLOADS if args.all and args.gpus == 1 else BASELINE_LEGS)
+        args.only = ",".join((WORKLOADS if args.all and args.gpus == 1 else BASELINE_LEGS) if args.full else ("bashF",))
     bad = set(x for x in args.only.split(",") if x) - set(WORKLOADS)
     if bad:                                # fail before any GPU work, not with an empty JSON line
         ap.error(f"unknown --only name(s) {sorted(bad)}; choose from {list(WORKLOADS)}")
+    if args.dump_outputs and "bashF" not in args.only.split(","):
+        ap.error("--dump-outputs writes the bashF headline's outputs: --only must include bashF")
     return args
 
 
@@ -162,13 +179,14 @@ def main():
     c.hc = host_cpus()                        # cpu_count / affinity / cgroup quota: threads = what this process may really use
     c.cores = c.hc["threads"]
     c.H = eng.beltH()
-    # the only cross-GPU payload: expanded key (32 B) + ctr0 (16 B), broadcast once over RCCL
-    if dist.rank == 0:
-        kw, c0 = eng.beltCTRStart(c.H[128:160], c.H[192:208])      # ctr0 = E_K(iv) on the GPU
-    else:
-        kw, c0 = bytes(32), bytes(16)
-    blob = dist.bcast_bytes(kw + c0, 48)
-    c.kw, c.c0 = blob[:32], blob[32:]
+    # the only cross-GPU payload: expanded key (32 B) + ctr0 (16 B), broadcast once over RCCL (for the legs that encrypt)
+    if set(only) & {"ctr", "mixed", "modes"}:
+        if dist.rank == 0:
+            kw, c0 = eng.beltCTRStart(c.H[128:160], c.H[192:208])      # ctr0 = E_K(iv) on the GPU
+        else:
+            kw, c0 = bytes(32), bytes(16)
+        blob = dist.bcast_bytes(kw + c0, 48)
+        c.kw, c.c0 = blob[:32], blob[32:]
 
     import importlib
     for w in only:
@@ -204,7 +222,7 @@ def main():
     detail["host"] = {"cpus": c.hc, "device": torch.cuda.get_device_name(torch.cuda.current_device()), "engine": eng.version(),
                       "n_devices_visible": dist.ndev, "argv": sys.argv[1:]}
     if dist.rank == 0:
-        if bench_line.write_detail(detail, ROOT) is None:
+        if not args.full or bench_line.write_detail(detail, ROOT) is None:
             ln.pop("detail", None)
         for f in bench_line.figures(ln, detail):
             print(f)

@@ -12,23 +12,28 @@ def run(c):
     others, rates, strong, diag, hc, do_cpu, strong_leg = c.others, c.rates, c.strong, c.diag, c.hc, c.do_cpu, c.strong_leg
     n = 1 << 20
     st = torch.empty(192 * n, dtype=torch.uint8, device="cuda")
-    fill_seeded(st, 0xBA5F + dist.rank)                      # synthetic states, generated in HBM
+    fill = lambda: fill_seeded(st, 0xBA5F + dist.rank)  # noqa: E731  (synthetic states, generated in HBM)
+    fill()
     step = lambda: eng.bashF_batch_dev(st)  # noqa: E731
-    solo_el = solo_timed(dist, K, W, step) if N > 1 else None      # rank 0 alone, before the group run
-    el = timed(dist, K, W, step)
+    solo_el = solo_timed(dist, K, W, step) if N > 1 and args.full else None      # rank 0 alone, before the group run
+    el = timed(dist, K, W, step, reset=fill)                  # the timed steps start from the seeded states: W + K passes over them
+    if args.dump_outputs and dist.rank == 0:                  # what the last timed step left, before anything else touches st
+        dump_rows(args.dump_outputs, "bashF_states", st, 192, 0xBA5F)
     value = N * n * K / el
     ms_launch = timed.event_ms                                # hipEvents around the K timed launches themselves
     own = dist.gather((n * K / timed.own_wall, n / (ms_launch * 1e-3)))   # each rank's own wall-clock and event rates
     ach = BASHF_BYTES * n / (ms_launch * 1e-3) / 1e9
-    pmc = pmc_headline("bashF", n)                           # a replay, and only of this very launch (same kernel, 2^20 states)
+    pmc = pmc_headline("bashF", n) if args.full else None   # a replay, and only of this very launch (same kernel, 2^20 states)
     traffic, traffic_src = (pmc["hbm_bytes_per_launch"], pmc["source"]) if pmc else (None, None)
     # the shader clock the chip sustained (power: ~1.8-1.9 GHz under this kernel is normal; one box of the pool ran everything
-    # at half speed): measured on every rank, outside the timed region
-    try:
-        ghz_under, ghz_idle = shader_clock_under(step, ms_launch)
-        clock_note = None if ghz_under else "libb2hprobe.so not built"
-    except Exception as e:                                    # the probe is a diagnostic, never a reason to fail the bench
-        ghz_under, ghz_idle, clock_note = None, None, repr(e)
+    # at half speed): measured on every rank, outside the timed region, with --full (it launches the kernel ~80 more times)
+    ghz_under, ghz_idle, clock_note = None, None, "not measured: a run without --full"
+    if args.full:
+        try:
+            ghz_under, ghz_idle = shader_clock_under(step, ms_launch)
+            clock_note = None if ghz_under else "libb2hprobe.so not built"
+        except Exception as e:                                # the probe is a diagnostic, never a reason to fail the bench
+            ghz_under, ghz_idle, clock_note = None, None, repr(e)
     clocks = [g for g in dist.gather(ghz_under) if g]
     result.update({
         "metric": "bashF perms/s", "value": value, "unit": "perms/s", "n_gpus": N, "steps": K, "warmup": W,

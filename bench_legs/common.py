@@ -240,15 +240,18 @@ class Dist:
             self.dist.destroy_process_group()
 
 
-def timed(dist, steps, warmup, fn):
+def timed(dist, steps, warmup, fn, reset=None):
     """clock pre-warm, W untimed steps, then exactly K timed steps between
-    barrier+synchronize pairs; returns the max over ranks of the elapsed seconds"""
+    barrier+synchronize pairs; returns the max over ranks of the elapsed seconds.  reset(), if given, runs between the pre-warm
+    and the W steps: an in-place step then sees the same input in every run, however many pre-warm launches there were"""
     # the chip needs a few hundred ms of load to reach its sustained clock (DVFS); without this
     # the first launches of a short run are ~8 % slower than steady state (tools/gap_test.py)
     t_end = time.perf_counter() + 0.3
     while time.perf_counter() < t_end:
         fn()
         torch.cuda.synchronize()
+    if reset is not None:
+        reset()
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
@@ -353,6 +356,19 @@ def fill_seeded(t, seed):
     g = torch.Generator(device="cuda")
     g.manual_seed(seed)
     t.view(torch.int64).random_(generator=g)
+
+
+DUMP_SAMPLE = 1 << 16            # rows per dumped output: 2^16 bashF states = 24 MiB as float64 words
+
+
+def dump_rows(dirpath, name, buf, row_bytes, seed):
+    """--dump-outputs: a fixed, seeded sample of the rows of the device buffer `buf` (row_bytes each) to dirpath/name.npy, as
+    float64 rows of little-endian 32-bit words (exact), sample rows in ascending index order"""
+    n = buf.numel() // row_bytes
+    idx = np.sort(np.random.default_rng(seed).choice(n, min(n, DUMP_SAMPLE), replace=False))
+    rows = buf.view(n, row_bytes)[torch.from_numpy(idx).to(buf.device)].cpu().numpy()
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(rows).view("<u4").astype(np.float64))
 
 
 def host_api_rate(call, units, reps=3):

@@ -89,7 +89,7 @@ def build(result, others, strong, diag, n_ranks, n_ranks_seen, n_distinct, lds_c
     line["roofline"] = flat
     if cb.get("kind") is None:
         cb = {"value": None, "unit": result.get("unit"), "cores": cb.get("cores"), "kind": None,
-              "sample": "not timed: cpu_baseline runs on rank 0 at N=1 only" if n_ranks > 1 else "not timed (--no-cpu)"}
+              "sample": "not timed: cpu_baseline runs on rank 0 at N=1 only" if n_ranks > 1 else "not timed (a run without --full, or --no-cpu)"}
     line["cpu_baseline"] = {k: cb.get(k) for k in CPU_KEYS if k in cb or k in ("value", "unit", "cores", "kind", "sample")}
     if n_ranks > 1:                                         # the N > 1 line explains itself: rank 0 alone beforehand, each rank's own rate, clocks
         line["ranks"] = {k: diag.get(k) for k in ("solo_value", "weak_efficiency", "per_rank_value_min", "per_rank_value_max",

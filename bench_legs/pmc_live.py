@@ -22,7 +22,7 @@ def _one_pass(counters, leg, timeout_s):
     tmp = tempfile.mkdtemp(prefix="b2h_pmc_", dir="/tmp")
     try:
         cmd = [exe, "--pmc"] + counters + ["--output-format", "csv", "-d", tmp, "-o", "b", "--",
-               sys.executable, os.path.join(ROOT, "bench.py"), "--only", leg, "--headline-only", "--no-cpu", "--no-live-pmc",
+               sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--only", leg, "--headline-only", "--no-cpu", "--no-live-pmc",
                "--steps", "5", "--warmup", "2"]
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
         env["TMPDIR"] = "/tmp"

@@ -20,14 +20,14 @@ def _run(extra, env_extra=None, timeout=240):
 
 @pytest.mark.parametrize("n", [2, 3])
 def test_bench_self_launches_n_ranks(n):
-    r = _run(["--gpus", str(n), "--launch-selftest"])
+    r = _run(["--gpus", str(n), "--launch-selftest", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout          # rank 0 prints ONE line
     d = json.loads(lines[0])
     assert d["n_gpus"] == n and d["roofline"]["n_ranks_seen"] == n and d["max_rank"] == n - 1
     assert d["roofline"]["n_devices_distinct"] == n          # (each rank reports its own stand-in device on CPU)
-    assert d["only"] == "bashF,ctr,verify,mixed"             # N > 1 default: the four BASELINE workloads, not the N = 1 legs
+    assert d["only"] == "bashF,ctr,verify,mixed"             # N > 1 --full default: the four BASELINE workloads, not the N = 1 legs
     # the strong (fixed-N) split of SURVEY 8e: the ranks' shard_range shares of each BASELINE job add up to the job, and the line
     # of an N-rank run carries one measured speedup per workload
     assert d["strong_keys"] == ["strong_speedup_bashF", "strong_speedup_ctr", "strong_speedup_verify", "strong_speedup_mixed"]
@@ -193,7 +193,7 @@ def test_bench_line_on_the_gpu_is_short_strict_and_complete():
     """the real thing, short: the four BASELINE legs on 1 GiB of stream, 3 steps; the LAST stdout line is the contract's line (<= 8000
     characters, strict JSON), the figures are in range, and the full record is in gpurun_out/bench_detail.json"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "BEE2_BENCH_BACKEND")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "3", "--warmup", "1",
                         "--ctr-gib", "1"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _check_line_shape(_last_line(r.stdout), 1)
@@ -238,13 +238,53 @@ def test_bench_line_on_the_gpu_is_short_strict_and_complete():
         assert det["others"]["bashF_detail"]["traffic_live"]["launches"] >= 5
 
 
+def test_plain_run_is_the_headline_alone_and_full_keeps_the_rest():
+    b = _bench_module()
+    a = b.parse(["--steps", "7", "--warmup", "2"])
+    assert a.only == "bashF" and not a.full and a.headline_only and a.no_cpu and a.no_live_pmc and a.steps == 7
+    a = b.parse(["--full"])
+    assert a.only == "bashF,ctr,verify,mixed" and not (a.headline_only or a.no_cpu or a.no_live_pmc)
+    assert b.parse(["--all"]).full and b.parse(["--all"]).only == ",".join(b.WORKLOADS)
+    with pytest.raises(SystemExit):
+        b.parse(["--dump-outputs", "x", "--only", "ctr"])
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_dumps_what_its_last_step_computed(orc, tmp_path):
+    """a plain run times K bashF steps on the seeded states and --dump-outputs writes the seeded sample of what the last one left:
+    the oracle's bashF applied W + K times to the same seeded input, so equal arguments give equal outputs"""
+    import numpy as np
+    import torch
+    from bench_legs.common import fill_seeded
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "BEE2_BENCH_BACKEND")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _check_line_shape(_last_line(r.stdout), 1)
+    assert d["metric"] == "bashF perms/s" and d["unit"] == "perms/s" and d["dtype"] == "u64" and d["higher_is_better"] is True
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and "detail" not in d
+    assert abs(d["value"] - (1 << 20) / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert d["cpu_baseline"]["value"] is None and d["roofline"]["beltCTR_GiBps"] is None and d["roofline"]["strong_pred_8_bashF"] is None
+    assert sorted(os.listdir(tmp_path)) == ["bashF_states.npy"]
+    got = np.load(tmp_path / "bashF_states.npy")
+    assert got.dtype == np.float64 and got.shape == (1 << 16, 48) and got.nbytes <= 64 << 20
+    n = 1 << 20
+    st = torch.empty(192 * n, dtype=torch.uint8, device="cuda")
+    fill_seeded(st, 0xBA5F)
+    idx = np.sort(np.random.default_rng(0xBA5F).choice(n, 1 << 16, replace=False))
+    want = np.ascontiguousarray(st.view(n, 192).cpu().numpy()[idx])
+    for _ in range(1 + 3):
+        orc.bashF_batch_np(want)
+    assert np.array_equal(got, want.view("<u4").astype(np.float64))
+
+
 @pytest.mark.gpu
 def test_bench_gpus_2_on_one_device_runs_two_ranks_and_explains_itself():
     """`python bench.py --gpus 2` as the driver would call it, on a one-GPU box: gloo collectives, both ranks on cuda:0.
     The line must carry what the first real 8-GPU run will need to be read: rank 0's solo rate, the weak-scaling
     efficiency against it (two ranks sharing ONE card: about 0.5 -- the documented value of this rehearsal), each rank's
     own rate, the number of distinct devices (1 here) and the clocks."""
-    r = _run(["--gpus", "2", "--steps", "10", "--warmup", "2", "--ctr-gib", "1"], timeout=1200)
+    r = _run(["--full", "--gpus", "2", "--steps", "10", "--warmup", "2", "--ctr-gib", "1"], timeout=1200)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

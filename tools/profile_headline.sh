@@ -19,7 +19,7 @@ LEGS=${LEGS:-"bashF ctr verify mixed"}
 SQ1="SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAVES SQ_INSTS_LDS"
 SQ2="SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INSTS_SALU SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES"
 for leg in $LEGS; do
-  CMD="python bench.py --only $leg --headline-only --no-cpu --steps 10 --warmup 2"
+  CMD="python bench.py --full --only $leg --headline-only --no-cpu --steps 10 --warmup 2"
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${leg}_stats -o b -- $CMD > $OUT/${leg}_stats.log 2>&1; echo "$leg stats rc=$?"
   timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/${leg}_fetch -o b -- $CMD > $OUT/${leg}_fetch.log 2>&1; echo "$leg fetch rc=$?"
   timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/${leg}_write -o b -- $CMD > $OUT/${leg}_write.log 2>&1; echo "$leg write rc=$?"
