@@ -86,7 +86,7 @@ __device__ __forceinline__ void bash_s_layer(u64x2 (&a)[24], const int (&ix)[24]
 // interleaves the two classes almost one for one (290 class switches per 6 rounds; staged: 24) and
 // puts consumers right behind their producers; gfx950 issues that order 3 % slower on the whole
 // bashF kernel (profiles/r01_valu_rates_ubench.txt "class-switch cost"; A/B log profiles/r01_bashF_ab_staged.txt).
-// Costs ~40 more live VGPRs (113 in bashF_batch_kernel).  The fused hash+MAC kernel, capped at 128
+// Costs ~40 more live VGPRs (113 in the r01 bashF kernel).  The fused hash+MAC kernel, capped at 128
 // VGPRs by its 1024-lane workgroups, spills 48-112 B per lane with it and is still 6 % faster
 // (profiles/r01_fused_ab_staged.txt: the spills are outside the round loop); with 768-lane
 // workgroups (no spills, 3 wavefronts per SIMD instead of 4) it loses 1 %.
@@ -146,8 +146,7 @@ template <int C> __device__ __forceinline__ void st_rot3(BashStage &q, u64x2 (&a
 }
 template <int C> __device__ __forceinline__ void st_rot1(BashStage &q) { q.r2[C] = vrotl64<BashRotC<C>::n2>(q.t[C]); }
 
-// PRIO: raise the wavefront's issue priority for the half-rate runs (see bash_prio_half / bash_prio_full below)
-template <bool PRIO = false>
+// the wavefront's issue priority is raised for the half-rate runs (bash_prio_half / bash_prio_full above)
 __device__ __forceinline__ void bash_s_layer_staged(u64x2 (&a)[24], const int (&ix)[24])
 {
     BashStage q;
@@ -156,18 +155,18 @@ __device__ __forceinline__ void bash_s_layer_staged(u64x2 (&a)[24], const int (&
         q.u0[c].lo = vbitop3<TT_XOR3>(a[ix[c]].lo, a[ix[8 + c]].lo, a[ix[16 + c]].lo);
         q.u0[c].hi = vbitop3<TT_XOR3>(a[ix[c]].hi, a[ix[8 + c]].hi, a[ix[16 + c]].hi);
     }
-    if constexpr (PRIO) bash_prio_half();
+    bash_prio_half();
     st_rot3<0>(q, a, ix); st_rot3<1>(q, a, ix); st_rot3<2>(q, a, ix); st_rot3<3>(q, a, ix);
     st_rot3<4>(q, a, ix); st_rot3<5>(q, a, ix); st_rot3<6>(q, a, ix); st_rot3<7>(q, a, ix);
-    if constexpr (PRIO) bash_prio_full();
+    bash_prio_full();
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         q.t[c].lo = vxor(a[ix[8 + c]].lo, q.ra[c].lo);  q.t[c].hi = vxor(a[ix[8 + c]].hi, q.ra[c].hi);
         q.u1[c].lo = vxor(q.t[c].lo, q.rb[c].lo);       q.u1[c].hi = vxor(q.t[c].hi, q.rb[c].hi);
     }
-    if constexpr (PRIO) bash_prio_half();
+    bash_prio_half();
     st_rot1<0>(q); st_rot1<1>(q); st_rot1<2>(q); st_rot1<3>(q); st_rot1<4>(q); st_rot1<5>(q); st_rot1<6>(q); st_rot1<7>(q);
-    if constexpr (PRIO) bash_prio_full();
+    bash_prio_full();
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         u64x2 u2;
@@ -185,7 +184,7 @@ __device__ __forceinline__ void bash_s_layer_staged(u64x2 (&a)[24], const int (&
 // pads every such asm -> asm dependency with an s_nop, 81 of them per 6 rounds, and the wavefront stalls on
 // the VALU latency anyway), and (ii) the stage width W is a parameter: W = 8 is one pass over all columns
 // (temporaries for 8 columns live), W = 4 two passes over 4 columns each (half the temporaries, shorter
-// runs of one instruction class).
+// runs of one instruction class; the product).
 template <int C0, int W, int K = 0>
 __device__ __forceinline__ void st2_rot3(u64x2 (&ra)[8], u64x2 (&rb)[8], u64x2 (&rc)[8], const u64x2 (&u0)[8],
                                          u64x2 (&a)[24], const int (&ix)[24])
@@ -206,7 +205,7 @@ __device__ __forceinline__ void st2_rot1(u64x2 (&r2)[8], const u64x2 (&t)[8])
         st2_rot1<C0, W, K + 1>(r2, t);
     }
 }
-template <int C0, int W, bool PRIO>
+template <int C0, int W>
 __device__ __forceinline__ void bash_s_cols_staged2(u64x2 (&a)[24], const int (&ix)[24])
 {
     u64x2 u0[8], ra[8], rb[8], rc[8], t[8], u1[8], r2[8], u2[8];
@@ -215,16 +214,16 @@ __device__ __forceinline__ void bash_s_cols_staged2(u64x2 (&a)[24], const int (&
         u0[c].lo = vbitop3<TT_XOR3>(a[ix[c]].lo, a[ix[8 + c]].lo, a[ix[16 + c]].lo);
         u0[c].hi = vbitop3<TT_XOR3>(a[ix[c]].hi, a[ix[8 + c]].hi, a[ix[16 + c]].hi);
     }
-    if constexpr (PRIO) bash_prio_half();
+    bash_prio_half();
     st2_rot3<C0, W>(ra, rb, rc, u0, a, ix);
-    if constexpr (PRIO) bash_prio_full();
+    bash_prio_full();
 #pragma unroll
     for (int c = C0; c < C0 + W; ++c) { t[c].lo = vxor(a[ix[8 + c]].lo, ra[c].lo); t[c].hi = vxor(a[ix[8 + c]].hi, ra[c].hi); }
 #pragma unroll
     for (int c = C0; c < C0 + W; ++c) { u1[c].lo = vxor(t[c].lo, rb[c].lo); u1[c].hi = vxor(t[c].hi, rb[c].hi); }
-    if constexpr (PRIO) bash_prio_half();
+    bash_prio_half();
     st2_rot1<C0, W>(r2, t);
-    if constexpr (PRIO) bash_prio_full();
+    bash_prio_full();
 #pragma unroll
     for (int c = C0; c < C0 + W; ++c) {
         u2[c].lo = vbitop3<TT_XOR3>(a[ix[16 + c]].lo, rc[c].lo, r2[c].lo);
@@ -237,12 +236,11 @@ __device__ __forceinline__ void bash_s_cols_staged2(u64x2 (&a)[24], const int (&
         a[ix[16 + c]].lo = vbitop3<TT_S2>(u0[c].lo, u1[c].lo, u2[c].lo);  a[ix[16 + c]].hi = vbitop3<TT_S2>(u0[c].hi, u1[c].hi, u2[c].hi);
     }
 }
-template <int W, bool PRIO = false>
+// W = 4, priority following the instruction class (the product of the r02 A/B)
 __device__ __forceinline__ void bash_s_layer_staged2(u64x2 (&a)[24], const int (&ix)[24])
 {
-    if constexpr (W == 8) bash_s_cols_staged2<0, 8, PRIO>(a, ix);
-    else if constexpr (W == 4) { bash_s_cols_staged2<0, 4, PRIO>(a, ix); bash_s_cols_staged2<4, 4, PRIO>(a, ix); }
-    else { bash_s_cols_staged2<0, 2, PRIO>(a, ix); bash_s_cols_staged2<2, 2, PRIO>(a, ix); bash_s_cols_staged2<4, 2, PRIO>(a, ix); bash_s_cols_staged2<6, 2, PRIO>(a, ix); }
+    bash_s_cols_staged2<0, 4>(a, ix);
+    bash_s_cols_staged2<4, 4>(a, ix);
 }
 
 // logical word k of the next round = logical word BASH_PERM[k] of this round:
@@ -278,20 +276,15 @@ __device__ __forceinline__ uint64_t bash_next_const(uint64_t c)
     return (c >> 1) ^ (0xDC2BE1997FE0D8AEull & (0ull - (c & 1ull)));
 }
 
-// ORDER: 0 = compiler's order ("compact"), 1 = staged (r01), 28 / 24 / 22 = staged, second form, W = 8 / 4 / 2;
-// +100: issue priority follows the instruction class
+// ORDER: 0 = compiler's order ("compact"), 101 = staged (r01), 124 = staged, second form, W = 4; both with the issue
+// priority following the instruction class.  The other orders of the r01 / r02 A/B are retired (profiles/r02_bashF_variants.txt).
 template <int R, int ORDER>
 __device__ __forceinline__ void bash_round(u64x2 (&a)[24], uint64_t &c)
 {
+    static_assert(ORDER == 0 || ORDER == 101 || ORDER == 124, "issue order");
     constexpr BashSlots S{};
-    if constexpr (ORDER == 1)        bash_s_layer_staged<false>(a, S.m[R]);
-    else if constexpr (ORDER == 101) bash_s_layer_staged<true>(a, S.m[R]);
-    else if constexpr (ORDER == 28)  bash_s_layer_staged2<8>(a, S.m[R]);
-    else if constexpr (ORDER == 24)  bash_s_layer_staged2<4>(a, S.m[R]);
-    else if constexpr (ORDER == 22)  bash_s_layer_staged2<2>(a, S.m[R]);
-    else if constexpr (ORDER == 128) bash_s_layer_staged2<8, true>(a, S.m[R]);
-    else if constexpr (ORDER == 124) bash_s_layer_staged2<4, true>(a, S.m[R]);
-    else if constexpr (ORDER == 122) bash_s_layer_staged2<2, true>(a, S.m[R]);
+    if constexpr (ORDER == 101)      bash_s_layer_staged(a, S.m[R]);
+    else if constexpr (ORDER == 124) bash_s_layer_staged2(a, S.m[R]);
     else                            bash_s_layer(a, S.m[R]);
     // after the word permutation the constant lands on logical word 23 of the next round
     constexpr int slot = S.m[R + 1][23];

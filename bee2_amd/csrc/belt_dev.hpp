@@ -172,110 +172,18 @@ struct BeltTabTwo {
     }
 };
 
-// EXPERIMENT (round 3; tools/ab/belt_ab.py variants 10 / 11, profiles/r03_belt_hybrid.txt): the two-table
-// LDS layout for most G-boxes, and every G-box for which `via_l1<R0, SLOT>()` says so looked up through the vector L1
-// instead -- four rotated tables of 256 dwords in global memory (4 KiB, L1-resident), one global_load_dword per byte
-// with the table selector in the immediate offset -- so that TA/TCP cycles run beside the LDS pipe.  Not the product.
-extern __device__ uint32_t d_beltT4[1024];
-template <int ROUNDS>                  // bit i-1 set: the last G-box of round i goes through the L1
-struct BeltTabHyb : BeltTabTwo {
-    __device__ explicit BeltTabHyb(const uint8_t *l) : BeltTabTwo(l) {}
-    template <int R0>
-    __device__ __forceinline__ GParts g_l1(uint32_t x) const
-    {
-        const uint32_t o0 = shl_c<2>(x) & 0x3FCu, o1 = shr_c<6>(x) & 0x3FCu, o2 = shr_c<14>(x) & 0x3FCu, o3 = shr_c<22>(x) & 0x3FCu;
-        const uint8_t *t = reinterpret_cast<const uint8_t *>(d_beltT4);
-        const uint32_t t0 = *reinterpret_cast<const uint32_t *>(t + ((R0 + 0) & 3) * 1024 + o0);
-        const uint32_t t1 = *reinterpret_cast<const uint32_t *>(t + ((R0 + 1) & 3) * 1024 + o1);
-        const uint32_t t2 = *reinterpret_cast<const uint32_t *>(t + ((R0 + 2) & 3) * 1024 + o2);
-        const uint32_t t3 = *reinterpret_cast<const uint32_t *>(t + ((R0 + 3) & 3) * 1024 + o3);
-        GParts r;
-        r.p = xor3(t0, t1, t2);
-        r.q = t3;
-        return r;
-    }
-    // SLOT = position of the G-box inside its round (0..6), I = round (1..8)
-    template <int R0, int SLOT, int I>
-    __device__ __forceinline__ GParts gs(uint32_t x) const
-    {
-        if constexpr (SLOT == 6 && ((ROUNDS >> (I - 1)) & 1)) return g_l1<R0>(x);
-        else return BeltTabTwo::template g<R0>(x);
-    }
-};
-
-// EXPERIMENT (round 3, tools/ab/belt_ab.py variant 15, profiles/r03_belt_sdwa_ab.txt): the two-table layout with every LDS address
-// made by ONE instruction.  The address is (byte << 8) | lane_base with lane_base < 128: byte 1 of a register whose other
-// bytes hold lane_base for good.  v_mov_b32_sdwa with dst_sel:BYTE_1 and dst_unused:UNUSED_PRESERVE drops byte k of x there
-// (half rate: the cycles of the shift + v_bitop3 pair it replaces, one issue slot instead of two).  Each G-box position of
-// the round owns its three address registers so that the two G-boxes the compiler keeps in flight do not meet in one.
-struct BeltTabTwoS : BeltTabTwo {
-    mutable uint32_t ar[7][3];
-    __device__ explicit BeltTabTwoS(const uint8_t *l) : BeltTabTwo(l)
-    {
-#pragma unroll
-        for (int s = 0; s < 7; ++s)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) ar[s][k] = base;
-    }
-    template <int R0, int SLOT, int I>
-    __device__ __forceinline__ GParts gs(uint32_t x) const
-    {
-        uint32_t &a0 = ar[SLOT][0], &a2 = ar[SLOT][1], &a3 = ar[SLOT][2];
-        asm("v_mov_b32_sdwa %0, %1 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_0" : "+v"(a0) : "v"(x));
-        const uint32_t a1 = and_or(x, 0xFF00u, base);
-        asm("v_mov_b32_sdwa %0, %1 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_2" : "+v"(a2) : "v"(x));
-        asm("v_mov_b32_sdwa %0, %1 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_3" : "+v"(a3) : "v"(x));
-        constexpr int r0 = (R0 + 0) & 3, r1 = (R0 + 1) & 3, r2 = (R0 + 2) & 3, r3 = (R0 + 3) & 3;
-        uint32_t t0 = *(lds_u32 *)(uintptr_t)(a0 + (r0 == 3 ? 128 : 0));
-        uint32_t t1 = *(lds_u32 *)(uintptr_t)(a1 + (r1 == 3 ? 128 : 0));
-        uint32_t t2 = *(lds_u32 *)(uintptr_t)(a2 + (r2 == 3 ? 128 : 0));
-        uint32_t t3 = *(lds_u32 *)(uintptr_t)(a3 + (r3 == 3 ? 128 : 0));
-        if (r0 == 1 || r0 == 2) t0 <<= 8 * r0;
-        if (r1 == 1 || r1 == 2) t1 <<= 8 * r1;
-        if (r2 == 1 || r2 == 2) t2 <<= 8 * r2;
-        if (r3 == 1 || r3 == 2) t3 <<= 8 * r3;
-        GParts r;
-        r.p = xor3(t0, t1, t2);
-        r.q = t3;
-        return r;
-    }
-};
-
-// EXPERIMENT (variant 16): BeltTabTwoS with the two post-shifts and the first xor folded into two v_lshl_or_b32 (the three T5
-// entries of a G-box occupy disjoint bit ranges once shifted): ((t_<<16 << 8) | t_<<8) << 8 | t_<<0 -- 8 VALU instructions per
-// G-box instead of 9, two of them half rate.
-struct BeltTabTwoL : BeltTabTwoS {
-    __device__ explicit BeltTabTwoL(const uint8_t *l) : BeltTabTwoS(l) {}
-    template <int R0, int SLOT, int I>
-    __device__ __forceinline__ GParts gs(uint32_t x) const
-    {
-        uint32_t &a0 = ar[SLOT][0], &a2 = ar[SLOT][1], &a3 = ar[SLOT][2];
-        asm("v_mov_b32_sdwa %0, %1 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_0" : "+v"(a0) : "v"(x));
-        const uint32_t a1 = and_or(x, 0xFF00u, base);
-        asm("v_mov_b32_sdwa %0, %1 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_2" : "+v"(a2) : "v"(x));
-        asm("v_mov_b32_sdwa %0, %1 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_3" : "+v"(a3) : "v"(x));
-        const uint32_t a[4] = {a0, a1, a2, a3};
-        uint32_t t[4];                               // t[r]: the entry whose rotation is 5 + 8 r
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int r = (R0 + k) & 3;
-            t[r] = *(lds_u32 *)(uintptr_t)(a[k] + (r == 3 ? 128 : 0));
-        }
-        uint32_t u, v;
-        asm("v_lshl_or_b32 %0, %1, 8, %2" : "=v"(u) : "v"(t[2]), "v"(t[1]));
-        asm("v_lshl_or_b32 %0, %1, 8, %2" : "=v"(v) : "v"(u), "v"(t[0]));
-        GParts g;
-        g.p = v;
-        g.q = t[3];
-        return g;
-    }
-};
-
-// The round-3 product table of the bank-private kernels: BeltTabTwoL with THREE address-register sets instead of seven
-// (G-boxes that can be in flight together never share one: slots 0..6 of a round use sets 0 1 0 1 0 1 2, and slot 6 never
-// meets slot 0 of the next round in the same set), so that the kernels built around 64 VGPRs keep their occupancy.
+// The round-3 product table of the bank-private kernels: the two-table layout with every LDS address made by ONE
+// instruction (profiles/r03_belt_sdwa_ab.txt).  The address is (byte << 8) | lane_base with lane_base < 128: byte 1 of a
+// register whose other bytes hold lane_base for good.  v_mov_b32_sdwa with dst_sel:BYTE_1 and dst_unused:UNUSED_PRESERVE
+// drops byte k of x there (half rate: the cycles of the shift + v_bitop3 pair it replaces, one issue slot instead of two).
+// The two post-shifts and the first xor fold into two v_lshl_or_b32 (the three T5 entries of a G-box occupy disjoint bit
+// ranges once shifted): 8 VALU instructions per G-box instead of 12.  THREE address-register sets (G-boxes that can be in
+// flight together never share one: slots 0..6 of a round use sets 0 1 0 1 0 1 2, and slot 6 never meets slot 0 of the
+// next round in the same set), so that the kernels built around 64 VGPRs keep their occupancy.  ONEWAIT = true (one
+// s_waitcnt per G-box) was measured and retired; the parameter stays because it is part of the kernels' names.
 template <bool ONEWAIT>
 struct BeltTabTwoPT : BeltTabTwo {
+    static_assert(!ONEWAIT, "the product form");
     mutable uint32_t ar[3][3];
     __device__ explicit BeltTabTwoPT(const uint8_t *l) : BeltTabTwo(l)
     {
@@ -300,9 +208,6 @@ struct BeltTabTwoPT : BeltTabTwo {
             const int r = (R0 + k) & 3;
             t[r] = *(lds_u32 *)(uintptr_t)(a[k] + (r == 3 ? 128 : 0));
         }
-        // ONEWAIT (experiment, variant 22): all four entries asked for at one point, so that ONE s_waitcnt serves the G-box
-        // instead of one per first use (the entries come back in order, a few cycles apart)
-        if constexpr (ONEWAIT) asm("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
         uint32_t u, v;
         asm("v_lshl_or_b32 %0, %1, 8, %2" : "=v"(u) : "v"(t[2]), "v"(t[1]));
         asm("v_lshl_or_b32 %0, %1, 8, %2" : "=v"(v) : "v"(u), "v"(t[0]));
@@ -313,7 +218,6 @@ struct BeltTabTwoPT : BeltTabTwo {
     }
 };
 typedef BeltTabTwoPT<false> BeltTabTwoP;
-typedef BeltTabTwoPT<true> BeltTabTwoQ;
 
 struct BeltTabSmall {
     static constexpr int kBytes = 4 * 256 * 4;             // 4096
@@ -340,35 +244,10 @@ struct BeltTabSmall {
     }
 };
 
-// EXPERIMENT (round 4, tools/ab/long_hash_ab.py form 4): BeltTabSmall with each look-up address made by ONE instruction,
-// v_lshlrev_b32_sdwa (byte k of x, shifted by 2), instead of extract + shift -- one dependent instruction less on a chain that is
-// bound by dependent latency (profiles/r04_long_hash_ab.txt).  Same table, same bank behaviour.
-struct BeltTabSmallS : BeltTabSmall {
-    __device__ explicit BeltTabSmallS(const uint8_t *l) : BeltTabSmall(l) {}
-    template <int R0>
-    __device__ __forceinline__ GParts g(uint32_t x) const
-    {
-        uint32_t a0, a1, a2, a3;
-        const uint32_t two = 2u;
-        asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(a0) : "v"(two), "v"(x));
-        asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(a1) : "v"(two), "v"(x));
-        asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(a2) : "v"(two), "v"(x));
-        asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(a3) : "v"(two), "v"(x));
-        const uint32_t t0 = *reinterpret_cast<const uint32_t *>(lds + ((R0 + 0) & 3) * 1024 + a0);
-        const uint32_t t1 = *reinterpret_cast<const uint32_t *>(lds + ((R0 + 1) & 3) * 1024 + a1);
-        const uint32_t t2 = *reinterpret_cast<const uint32_t *>(lds + ((R0 + 2) & 3) * 1024 + a2);
-        const uint32_t t3 = *reinterpret_cast<const uint32_t *>(lds + ((R0 + 3) & 3) * 1024 + a3);
-        GParts r;
-        r.p = xor3(t0, t1, t2);
-        r.q = t3;
-        return r;
-    }
-};
-
 // G_r(x), r = 5 + 8*R0 (belt_block.c:210-215): table (R0 + k) & 3 serves byte k of x.
 // G5 = g<0>, G13 = g<1>, G21 = g<2>.
 
-// G-box number SLOT of a round: tables with a slot-aware accessor (BeltTabHyb) choose their path by it
+// G-box number SLOT of a round: tables with a slot-aware accessor (BeltTabTwoPT) choose their registers by it
 template <int R0, int SLOT, int I, class Tab>
 __device__ __forceinline__ auto gbox(const Tab &T, uint32_t x, int) -> decltype(T.template gs<R0, SLOT, I>(x))
 {
@@ -619,117 +498,10 @@ __device__ __forceinline__ void belt_compress_pair(const Tab &T, uint32_t (&s1)[
     }
 }
 
-// ---- E_K walked by a PAIR of lanes (round 4: long belt-hash chains) -------------------------------------------------------
-// A lone chain is bound by the latency of its dependent instructions and LDS round trips (profiles/r04_long_hash_ab.txt), and
-// the seven G-boxes of a round have dependency depth FOUR:
-//     level 1   b ^= G5(a + k0)        ||  c ^= G21(d + k1)
-//     level 2   a -= G13(b + k2)       ||  e = G21(b + c + k3) ^ i;  b += e;  c -= e
-//     level 3   d += G13(c + k4)       ||  b ^= G21(a + k5)
-//     level 4   c ^= G5(d + k6)
-// Lane P (rQ = 0) takes the left column, lane Q (rQ = all-ones) the right one; each G-box result goes to the partner by DPP
-// (quad_perm 1,0,3,2), folded into the consuming instruction where the compiler can.  So that both lanes run the SAME
-// instructions on the same registers, Q keeps the state mirrored -- (w, u, v, z) = (a, b, c, d) in P, (d, c, b, a) in Q -- its
-// round keys shifted by one (Ks[j] = K[j + 1]), and the rotation its G-box needs on top of the table's (G21 from the G5 / G13
-// look-up: 16 / 8 more) is one v_alignbit with a per-lane amount.  Both lanes end with the whole block.
-__device__ __forceinline__ uint32_t dpp_swap1(uint32_t x)      // the value of the other lane of the pair
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, false);    // quad_perm [1, 0, 3, 2]
-}
-template <int I, class Tab>
-__device__ __forceinline__ void belt_round_split(const Tab &T, uint32_t &w, uint32_t &u, uint32_t &v, uint32_t &z,
-                                                 const uint32_t (&K)[8], const uint32_t (&Ks)[8], uint32_t rQ, uint32_t sh16,
-                                                 uint32_t sh8)
-{
-    constexpr int o = 7 * I - 7;
-    const uint32_t nQ = ~rQ;
-    GParts g;
-    uint32_t gg, og, t;
-    // level 1
-    g = T.template g<0>(w + Ks[(o + 0) & 7]);
-    gg = __builtin_amdgcn_alignbit(g.p ^ g.q, g.p ^ g.q, sh16);
-    u ^= gg;
-    v ^= dpp_swap1(gg);
-    // level 2
-    g = T.template g<1>(u + (v & rQ) + Ks[(o + 2) & 7]);
-    t = xor3(g.p, g.q, ((uint32_t)I << 24) & rQ);               // e = G21(..) ^ i: i goes in BEFORE the 8 extra bits of rotation
-    gg = __builtin_amdgcn_alignbit(t, t, sh8);
-    og = dpp_swap1(gg);
-    t = (og & nQ) | ((0u - gg) & rQ);                           // P: e from Q;  Q: -e (its own)
-    u += t;
-    v -= t;
-    w -= gg & nQ;                                               // P: a -= G13(b + k2)
-    z -= og & rQ;                                               // Q: the same a, from P
-    // level 3
-    g = T.template g<1>(((v & nQ) | (z & rQ)) + Ks[(o + 4) & 7]);
-    gg = __builtin_amdgcn_alignbit(g.p ^ g.q, g.p ^ g.q, sh8);
-    og = dpp_swap1(gg);
-    z += gg & nQ;                                               // P: d += G13(c + k4)
-    v ^= gg & rQ;                                               // Q: b ^= G21(a + k5)
-    u ^= og & nQ;                                               // P: b ^= (from Q)
-    w += og & rQ;                                               // Q: d += (from P)
-    // level 4: both lanes the same G-box
-    g = T.template g<0>(((z & nQ) | (w & rQ)) + K[(o + 6) & 7]);
-    t = g.p ^ g.q;
-    v ^= t & nQ;
-    u ^= t & rQ;
-}
-template <class Tab>
-__device__ __forceinline__ void belt_encr_split(const Tab &T, uint32_t (&x)[4], const uint32_t (&K)[8], uint32_t rQ)
-{
-    const uint32_t nQ = ~rQ;
-    const uint32_t sh16 = rQ & 16u, sh8 = rQ & 24u;             // v_alignbit amounts: rotate left by 16 / 8 in lane Q, by 0 in lane P
-    uint32_t Ks[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) Ks[j] = (K[j] & nQ) | (K[(j + 1) & 7] & rQ);
-    uint32_t w = (x[0] & nQ) | (x[3] & rQ), u = (x[1] & nQ) | (x[2] & rQ), v = (x[2] & nQ) | (x[1] & rQ), z = (x[3] & nQ) | (x[0] & rQ);
-    belt_round_split<1>(T, w, u, v, z, K, Ks, rQ, sh16, sh8);
-    belt_round_split<2>(T, u, z, w, v, K, Ks, rQ, sh16, sh8);
-    belt_round_split<3>(T, z, v, u, w, K, Ks, rQ, sh16, sh8);
-    belt_round_split<4>(T, v, w, z, u, K, Ks, rQ, sh16, sh8);
-    belt_round_split<5>(T, w, u, v, z, K, Ks, rQ, sh16, sh8);
-    belt_round_split<6>(T, u, z, w, v, K, Ks, rQ, sh16, sh8);
-    belt_round_split<7>(T, z, v, u, w, K, Ks, rQ, sh16, sh8);
-    belt_round_split<8>(T, v, w, z, u, K, Ks, rQ, sh16, sh8);
-    // logical (a, b, c, d) = (w, u, v, z) in P, (z, v, u, w) in Q; the block is (b, d, a, c)
-    x[0] = (u & nQ) | (v & rQ);
-    x[1] = (z & nQ) | (w & rQ);
-    x[2] = (w & nQ) | (z & rQ);
-    x[3] = (v & nQ) | (u & rQ);
-}
-
-// The compression by a QUAD of lanes that all hold h and X: lanes {0, 1} and {2, 3} are two such pairs; the first encryption
-// is walked by both pairs (the same values), the two independent ones of the second stage by one pair each (`odd` = all-ones
-// in lanes 2, 3), and the halves are swapped across the pairs.
-template <class Tab>
-__device__ __forceinline__ void belt_compress_quad(const Tab &T, uint32_t (&s1)[4], uint32_t (&h)[8], const uint32_t (&X)[8],
-                                                   uint32_t rQ /* lane bit 0 */, uint32_t odd /* lane bit 1 */)
-{
-    uint32_t uu[4], key[8], y[4], xs[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { uu[i] = h[i] ^ h[4 + i]; s1[i] = uu[i]; }
-    belt_encr_split(T, s1, X, rQ);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        s1[i] ^= uu[i];
-        key[i] = s1[i] ^ odd;                                   // s1 | ~s1
-        key[4 + i] = (h[4 + i] & ~odd) | (h[i] & odd);          // h1 | h0
-        xs[i] = (X[i] & ~odd) | (X[4 + i] & odd);               // X0 | X1
-        y[i] = xs[i];
-    }
-    belt_encr_split(T, y, key, rQ);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t mine = y[i] ^ xs[i];                     // h0' in lanes 0, 1; h1' in lanes 2, 3
-        const uint32_t other = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine, 0x4E, 0xF, 0xF, false);   // quad_perm [2, 3, 0, 1]
-        h[i] = (mine & ~odd) | (other & odd);
-        h[4 + i] = (other & ~odd) | (mine & odd);
-    }
-}
-
 // ---- E_K with every G-box shared by a QUAD of lanes, one S-box byte each (round 4) -----------------------------------------
-// The level-split above leaves the chain as slow as it was (profiles/r04_long_hash_ab.txt: same instruction count per lane --
-// a lone wavefront is bound by the instructions it issues, ~5 cycles each, with the LDS round trip mostly hidden).  This form
-// cuts the instructions per G-box instead: all four lanes of a quad hold the same (a, b, c, d) and compute x = a + k, lane j
+// Splitting a round's G-boxes over two lanes leaves the chain as slow as it was (profiles/r04_long_hash_ab.txt: same instruction
+// count per lane -- a lone wavefront is bound by the instructions it issues, ~5 cycles each, with the LDS round trip mostly
+// hidden; that form is retired).  This one cuts the instructions per G-box instead: all four lanes of a quad hold the same (a, b, c, d) and compute x = a + k, lane j
 // extracts byte j (v_bfe with its own shift), looks up ONE entry -- table (R0 + j) mod 4, a per-lane offset -- and two
 // v_xor_b32_dpp (quad_perm 1,0,3,2 then 2,3,0,1) leave G(x) in all four: add, bfe, shift-add, ds_read, wait, xor, xor, apply =
 // 8 instructions where one lane alone needs 13.

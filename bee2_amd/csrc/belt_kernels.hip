@@ -27,8 +27,6 @@
 
 namespace bee2hip {
 
-__device__ uint32_t d_beltT4[1024];       // experiment only (BeltTabHyb): rotl(S, 5 / 13 / 21 / 29), 4 x 256 dwords
-
 constexpr int CTR_WG = 1024;
 // 64 KiB, two workgroups (32 wavefronts) per CU; LDS addresses by one SDWA move each and the post-shifts folded into two
 // v_lshl_or_b32: 8 VALU instructions per G-box instead of 12 (round 3: beltCTR 835 -> 965 GiB/s on 16 GiB, profiles/r03_belt_sdwa_ab.txt)
@@ -61,19 +59,18 @@ __device__ __forceinline__ void ctr_at(uint32_t (&x)[4], const BeltCtr &c0, uint
     x[2] = (uint32_t)nhi; x[3] = (uint32_t)(nhi >> 32);
 }
 
-// Tab / ILP are template parameters so that the round-2 A/B (profiles/r02_belt_variants.txt)
-// runs the very same body: the product is <CtrTab, CTR_ILP>; the others are reachable only through
-// bee2hip_internal_tune(1, v).
-// MEM bit 2 (round 3): the counter's upper half does not change inside the launch (checked by launch_ctr_t): the second
+// Tab / ILP / MEM are the coordinates of the round-2 / round-3 A/B (profiles/r02_belt_variants.txt,
+// profiles/r03_belt_mem_ab.txt, profiles/r03_belt_sdwa_ab.txt); the product is <CtrTab, CTR_ILP, 3 | 7>, the other forms
+// are retired.  MEM bit 0 = non-temporal loads and stores of the stream (read once, written once), bit 1 = every workgroup
+// walks ONE contiguous range of tiles instead of taking every gridDim-th tile (a new 2 MiB page per tile and workgroup),
+// bit 2 = the counter's upper half does not change inside the launch (checked by launch_belt_ctr_blocks): the second
 // G-box of round 1 is hoisted out of the block loop (belt_encr_n_ctr).
-// MEM (round-3 A/B; profiles/r03_belt_mem_ab.txt): bit 0 = non-temporal loads and stores of the
-// stream (read once, written once), bit 1 = every workgroup walks ONE contiguous range of tiles instead of taking every
-// gridDim-th tile (a new 2 MiB page per tile and workgroup).
-template <class Tab, int ILP, int MEM = 0>
+template <class Tab, int ILP, int MEM>
 __global__ __launch_bounds__(CTR_WG, (BeltTabWide::kBytes / Tab::kBytes) * (CTR_WG / 256))
 void beltCTR_blocks_kernel(uint4 *__restrict__ buf, size_t nblocks, BeltKey key, BeltCtr ctr0,
                            uint64_t first, uint4 *__restrict__ last_gamma)
 {
+    static_assert((MEM & 3) == 3, "the product form: non-temporal stream, contiguous tile ranges");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     Tab::fill(smem, threadIdx.x, CTR_WG);
     __syncthreads();
@@ -83,7 +80,7 @@ void beltCTR_blocks_kernel(uint4 *__restrict__ buf, size_t nblocks, BeltKey key,
 #pragma unroll
     for (int i = 0; i < 8; ++i) K[i] = key.k[i];
 
-    // tile = CTR_WG * ILP consecutive blocks; tiles are dealt round-robin to workgroups
+    // tile = CTR_WG * ILP consecutive blocks; every workgroup takes one contiguous range of tiles
     uint32_t pre_c = 0;
     if constexpr ((MEM & 4) != 0) {
         uint32_t x0[4];
@@ -94,9 +91,9 @@ void beltCTR_blocks_kernel(uint4 *__restrict__ buf, size_t nblocks, BeltKey key,
     const size_t tile = (size_t)CTR_WG * ILP;
     const size_t ntiles = (nblocks + tile - 1) / tile;
     const size_t per_wg = (ntiles + gridDim.x - 1) / gridDim.x;
-    const size_t t_begin = (MEM & 2) ? (size_t)blockIdx.x * per_wg * tile : (size_t)blockIdx.x * tile;
-    const size_t t_end = (MEM & 2) ? ((size_t)blockIdx.x + 1) * per_wg * tile : nblocks;
-    const size_t t_step = (MEM & 2) ? tile : (size_t)gridDim.x * tile;
+    const size_t t_begin = (size_t)blockIdx.x * per_wg * tile;
+    const size_t t_end = ((size_t)blockIdx.x + 1) * per_wg * tile;
+    const size_t t_step = tile;
     for (size_t t0 = t_begin; t0 < nblocks && t0 < t_end; t0 += t_step) {
         uint4 data[ILP];
         uint32_t g[ILP][4];
@@ -105,7 +102,7 @@ void beltCTR_blocks_kernel(uint4 *__restrict__ buf, size_t nblocks, BeltKey key,
         for (int u = 0; u < ILP; ++u) {
             const size_t i = t0 + (size_t)u * CTR_WG + threadIdx.x;
             live[u] = i < nblocks;
-            if (live[u]) data[u] = (MEM & 1) ? nt_load16(&buf[i]) : buf[i];
+            if (live[u]) data[u] = nt_load16(&buf[i]);
             ctr_at(g[u], ctr0, first + i + 1);
         }
         if constexpr ((MEM & 4) != 0) belt_encr_n_ctr<ILP>(T, g, K, pre_c);
@@ -117,7 +114,7 @@ void beltCTR_blocks_kernel(uint4 *__restrict__ buf, size_t nblocks, BeltKey key,
                 uint4 o;
                 o.x = data[u].x ^ g[u][0]; o.y = data[u].y ^ g[u][1];
                 o.z = data[u].z ^ g[u][2]; o.w = data[u].w ^ g[u][3];
-                if (MEM & 1) nt_store16(&buf[i], o); else buf[i] = o;
+                nt_store16(&buf[i], o);
                 // streaming state needs the gamma of the final block (belt_ctr.c:89-96)
                 if (last_gamma && i == nblocks - 1)
                     *last_gamma = make_uint4(g[u][0], g[u][1], g[u][2], g[u][3]);
@@ -676,20 +673,10 @@ hipError_t dyn_lds_once(const void *kern, size_t bytes)
 err_t upload_beltH(const uint8_t *H)
 {
     B2H_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_beltH), H, 256));
-    uint32_t t4[1024];
-    for (int i = 0; i < 1024; ++i) {
-        const uint32_t v = H[i & 255];
-        const int r = 5 + 8 * (i >> 8);
-        t4[i] = (v << r) | (v >> (32 - r));
-    }
-    B2H_TRY(hipMemcpyToSymbol(HIP_SYMBOL(d_beltT4), t4, sizeof t4));
     return ERR_OK;
 }
 
-static int g_ctr_variant = 0;
-void set_ctr_variant(int v) { g_ctr_variant = v; }
-
-template <class Tab, int ILP, int MEM = 0>
+template <class Tab, int ILP, int MEM>
 static err_t launch_ctr_t(void *d_buf, size_t nblocks, const BeltKey &k, const BeltCtr &c, uint64_t first,
                           void *d_last_gamma, hipStream_t st)
 {
@@ -713,33 +700,6 @@ err_t launch_belt_ctr_blocks(void *d_buf, size_t nblocks, const uint32_t key[8],
     BeltKey k; BeltCtr c;
     for (int i = 0; i < 8; ++i) k.k[i] = key[i];
     for (int i = 0; i < 4; ++i) c.c[i] = ctr0[i];
-#ifdef BEE2HIP_EXPERIMENTS      // the A/B record (tools/ab/belt_ab.py; built by tools/ab/ab_lib.sh only)
-    switch (g_ctr_variant) {          // A/B only (bee2hip_internal_tune(1, v)); 0 = the product
-    case 1: return launch_ctr_t<BeltTabTwo, 2>(d_buf, nblocks, k, c, first, d_last_gamma, st);
-    case 2: return launch_ctr_t<BeltTabTwo, 3>(d_buf, nblocks, k, c, first, d_last_gamma, st);
-    case 3: return launch_ctr_t<BeltTabTwo, 4>(d_buf, nblocks, k, c, first, d_last_gamma, st);
-    case 4: return launch_ctr_t<BeltTabWide, 2>(d_buf, nblocks, k, c, first, d_last_gamma, st);
-    case 5: return launch_ctr_t<BeltTabWide, 3>(d_buf, nblocks, k, c, first, d_last_gamma, st);
-    case 6: return launch_ctr_t<BeltTabWide, 4>(d_buf, nblocks, k, c, first, d_last_gamma, st);
-    case 7: return launch_ctr_t<BeltTabTwo, CTR_ILP, 1>(d_buf, nblocks, k, c, first, d_last_gamma, st);
-    case 8: return launch_ctr_t<BeltTabTwo, CTR_ILP, 2>(d_buf, nblocks, k, c, first, d_last_gamma, st);
-    case 9: return launch_ctr_t<BeltTabTwo, CTR_ILP, 3>(d_buf, nblocks, k, c, first, d_last_gamma, st);
-    case 10: return launch_ctr_t<BeltTabHyb<0xFF>, 1>(d_buf, nblocks, k, c, first, d_last_gamma, st);   // 32 of 224 lookups via L1
-    case 11: return launch_ctr_t<BeltTabHyb<0x55>, 1>(d_buf, nblocks, k, c, first, d_last_gamma, st);   // 16
-    case 12: return launch_ctr_t<BeltTabHyb<0x11>, 1>(d_buf, nblocks, k, c, first, d_last_gamma, st);   // 8
-    case 13: return launch_ctr_t<BeltTabTwo, CTR_ILP, 0>(d_buf, nblocks, k, c, first, d_last_gamma, st);   // the round-2 product
-    case 14: return launch_ctr_t<BeltTabTwo, CTR_ILP, 3>(d_buf, nblocks, k, c, first, d_last_gamma, st);   // round 3 without the hoisted G-box
-    case 15: return launch_ctr_t<BeltTabTwoS, 1, 3>(d_buf, nblocks, k, c, first, d_last_gamma, st);    // one-instruction (SDWA) LDS addresses
-    case 16: return launch_ctr_t<BeltTabTwoL, 1, 3>(d_buf, nblocks, k, c, first, d_last_gamma, st);    // + v_lshl_or_b32 combine
-    case 17: return launch_ctr_t<BeltTabTwoS, 1, 7>(d_buf, nblocks, k, c, first, d_last_gamma, st);    // 15 + hoisted round-1 G-box
-    case 18: return launch_ctr_t<BeltTabTwoL, 1, 7>(d_buf, nblocks, k, c, first, d_last_gamma, st);    // 16 + hoisted round-1 G-box
-    case 19: return launch_ctr_t<BeltTabTwoS, 2, 7>(d_buf, nblocks, k, c, first, d_last_gamma, st);    // 17 with 2 blocks per lane
-    case 21: return launch_ctr_t<BeltTabTwo, 1, 7>(d_buf, nblocks, k, c, first, d_last_gamma, st);     // the product up to 4ab23f3
-    case 22: return launch_ctr_t<BeltTabTwoQ, 1, 7>(d_buf, nblocks, k, c, first, d_last_gamma, st);    // 20 with one s_waitcnt per G-box
-    case 20: return launch_ctr_t<BeltTabTwoP, 1, 7>(d_buf, nblocks, k, c, first, d_last_gamma, st);    // 18 with three address-register sets
-    default: break;
-    }
-#endif
     // product (round 3): contiguous tile ranges + non-temporal stream accesses, +1 % (profiles/r03_belt_mem_ab.txt); the table
     // type CtrTab = BeltTabTwoP (one-instruction LDS addresses), +15 % (profiles/r03_belt_sdwa_ab.txt)
     {

@@ -1305,9 +1305,9 @@ void bign_onekey4_kernel(const uint8_t *__restrict__ hashes, const uint8_t *__re
 // index i * 32 + j - 1; W6 = ceil((32N + 1) / 6) windows (43 / 65 / 86), the last one takes what is left of the scalar
 // plus the carry of the recoding (at most 16 / 1 / 4).  From the seed table: j 2^(6i) = lo 2^(8a) + hi 2^(8a + 8); the one
 // multiple outside it that a digit can ask for is 2^(32N) G = 2 (128 2^(32N - 8) G).  Entries no digit reaches are zero.
-// (round 4) WB = 7: the same with signed 7-bit windows -- 64 entries per window, ceil((32N + 1) / 7) windows (37 on the 256-bit
-// curve, whose top window starts at bit 252 like the 6-bit one's) -- for the kernel that looks its entry up in LDS
-// (bign_mulbase_lds_kernel): the row size no longer costs a masked scan there, so fewer, wider windows pay.
+// (round 4) WB = 8: the same with signed 8-bit windows -- 128 entries per window, ceil((32N + 1) / 8) windows -- for the kernel
+// that looks its entry up in LDS (bign_mulbase_lds_kernel): the row size no longer costs a masked scan there, so fewer, wider
+// windows pay.
 template <int N> struct Win6 { static constexpr int W = (32 * N + 1 + 5) / 6; };
 template <int N, int WB> struct WinW { static constexpr int W = (32 * N + 1 + WB - 1) / WB, ENT = 1 << (WB - 1); };
 template <int N, int WB = 6>
@@ -1498,8 +1498,7 @@ struct BignDevice {
     uint4 *gtab8[3] = {nullptr, nullptr, nullptr};     // 8-bit seed table per curve (index N/4 - 2): 4N x 256 affine points
     uint4 *gtab[3] = {nullptr, nullptr, nullptr};      // 16-bit comb table per curve, built from the seed table
     uint4 *gtab6[3] = {nullptr, nullptr, nullptr};     // signed 6-bit windows (signing side, one lane per scalar)
-    uint4 *gtab7[3] = {nullptr, nullptr, nullptr};     // signed 7-bit windows (signing side, LDS look-up kernel: 256-bit curve)
-    uint4 *gtabw8[3] = {nullptr, nullptr, nullptr};    // signed 8-bit windows (the same kernel with 16 copies of the row and 16-octet reads)
+    uint4 *gtabw8[3] = {nullptr, nullptr, nullptr};    // signed 8-bit windows (signing side, LDS look-up kernel: 256-bit curve)
 };
 static BignDevice g_bign[64];
 static std::mutex g_bign_mu;          // table construction is per device, shared by threads
@@ -1560,18 +1559,18 @@ static err_t bign_table6(const uint32_t **out8, const uint32_t **out6, hipStream
     return ERR_OK;
 }
 
-// the signed 7- / 8-bit window tables (148 / 264 KiB on the 256-bit curve), made from the seed table like the 6-bit one
+// the signed 8-bit window table (264 KiB on the 256-bit curve), made from the seed table like the 6-bit one
 template <int N, int WB>
 static err_t bign_tablew(const uint32_t **outw, hipStream_t st)
 {
-    static_assert(WB == 7 || WB == 8, "window tables of the LDS look-up kernel");
+    static_assert(WB == 8, "window table of the LDS look-up kernel");
     std::lock_guard<std::mutex> lk(g_bign_mu);
     uint4 *t8 = nullptr;
     err_t code = bign_table8_locked<N>(&t8, st);
     if (code != ERR_OK) return code;
     int dev = 0;
     B2H_TRY(hipGetDevice(&dev));
-    uint4 *&slot = (WB == 7 ? g_bign[dev].gtab7 : g_bign[dev].gtabw8)[N / 4 - 2];
+    uint4 *&slot = g_bign[dev].gtabw8[N / 4 - 2];
     if (!slot) {
         uint4 *tw = nullptr;
         const size_t entries = (size_t)WinW<N, WB>::W * WinW<N, WB>::ENT;
@@ -1627,44 +1626,12 @@ static err_t bign_scratch(hipStream_t st, size_t n, VerifyScratch &S)
     return ERR_OK;
 }
 
-static int g_inv_lanes_log2 = 0;                     // lanes of bign_inv_kernel (log2; 0 = by curve): A/B, tune 23
-void set_inv_lanes(int v) { g_inv_lanes_log2 = v; }
 static int g_verify_path = 0, g_verify_lanes = 0;
 void set_verify_path(int v) { g_verify_path = v & 15; g_verify_lanes = v >> 4; }   // 0x43: quads at every size
-static int g_verify_split = 0;                       // 0 = by size, 1 = never, 2 / 3 / 4 = that many parts (A/B)
-void set_verify_split(int v) { g_verify_split = v; }
-
-// EXPERIMENT (round 3, off by default): a big batch as PARTS on separate streams, each part its own prep -> main -> slow ->
-// inv -> tail chain, part p + 1 starting when part p's prep is through, so that the phases that leave the SIMDs half empty
-// -- prep (two wavefronts per SIMD around one serial inversion), inv (512 wavefronts on 1024 SIMDs), tail (LDS-bound) --
-// run beside another part's main kernel instead of alone.  It does not pay (profiles/r03_verify_split.txt).  The parts share the scratch (disjoint index ranges of the same
-// signature-fastest arrays) and the comb table; the caller's stream is forked and joined with events.
-struct AuxStreams {
-    hipStream_t s[3] = {nullptr, nullptr, nullptr};
-    int dev = -1;
-    err_t get()
-    {
-        int cur = 0;
-        B2H_TRY(hipGetDevice(&cur));
-        if (s[0] && cur == dev) return ERR_OK;
-        for (hipStream_t &x : s) { if (x) (void)hipStreamDestroy(x); x = nullptr; }
-        for (hipStream_t &x : s) B2H_TRY(hipStreamCreateWithFlags(&x, hipStreamNonBlocking));
-        dev = cur;
-        return ERR_OK;
-    }
-};
-// multiply-adds in pairs in the verification MAIN kernel: -1 = by curve and batch size (launch_bign_verify_t), 0 never, else always
-// (A/B: bee2hip_internal_tune 19)
-static int g_verify_pairs = -1;
-#ifdef BEE2HIP_EXPERIMENTS
-void set_verify_pairs(int v) { g_verify_pairs = v; }
-#endif
-static thread_local AuxStreams t_aux;
 
 template <int N>
-static err_t launch_bign_verify_t(const uint8_t *oid_der, size_t oid_len, const void *d_hashes_all,
-                                  const void *d_sigs_all, const void *d_pubkeys_all, size_t n, void *d_codes_all,
-                                  hipStream_t st)
+static err_t launch_bign_verify_t(const uint8_t *oid_der, size_t oid_len, const void *d_hashes, const void *d_sigs,
+                                  const void *d_pubkeys, size_t n, void *d_codes, hipStream_t st)
 {
     uint4 *gtab = nullptr;
     err_t code;
@@ -1673,26 +1640,15 @@ static err_t launch_bign_verify_t(const uint8_t *oid_der, size_t oid_len, const 
         code = bign_table<N>(&gtab, st);
     }
     if (code != ERR_OK) return code;
-    VerifyScratch S_all;
-    code = bign_scratch<N>(st, n, S_all);
+    VerifyScratch S;
+    code = bign_scratch<N>(st, n, S);
     if (code != ERR_OK) return code;
     OidArg oid;
     code = make_oid_arg(oid, oid_der, oid_len, st);
     if (code != ERR_OK) return code;
-    const size_t n_total = n;
     constexpr size_t NO_ = 4 * N;
-    // one chain over the signatures [off, off + cnt) on stream `st`; ev_prep (may be null) is recorded behind the prep kernel
-    const auto run_range = [&, gtab, oid](size_t off, size_t cnt, hipStream_t st, hipEvent_t ev_prep) -> err_t {
-    VerifyScratch S = S_all;
-    S.status += off; S.u += off; S.w += off; S.qtab += off; S.qz += off; S.rx += off;
-    const size_t n = cnt;
-    const uint8_t *d_hashes = (const uint8_t *)d_hashes_all + NO_ * off;
-    const uint8_t *d_sigs = (const uint8_t *)d_sigs_all + (NO_ + NO_ / 2) * off;
-    const uint8_t *d_pubkeys = (const uint8_t *)d_pubkeys_all + 2 * NO_ * off;
-    uint32_t *d_codes = (uint32_t *)d_codes_all + off;
-    err_t code = ERR_OK;
     const unsigned g256 = (unsigned)((n + 255) / 256), g64 = (unsigned)((n + 63) / 64);
-    const size_t sp = n_total >= ((size_t)1 << 18) ? 2 : 1;     // signatures per lane in prep (shared inversion)
+    const size_t sp = n >= ((size_t)1 << 18) ? 2 : 1;           // signatures per lane in prep (shared inversion)
     const size_t plan = (n + sp - 1) / sp;
     // Which kernels walk the scalar multiplication (g_verify_path: 0 by size, 1 always the 32-bit
     // kernels, 2 the 29-bit main kernel, 3 the quad / pair kernel, + 16 x lanes to force quads (0x43), pairs (0x23) or quads with a helper quad (0x83; 0x93 / 0xA3 with 64 / 256 lanes per block)
@@ -1730,27 +1686,22 @@ static err_t launch_bign_verify_t(const uint8_t *oid_der, size_t oid_len, const 
             const bool one_wave = g_verify_lanes == 9 || (g_verify_lanes != 10 && n > ((size_t)3 << 10) && n <= ((size_t)1 << 12));
             if (helper && one_wave) code = launch(bign_quad29_kernel<N, 64, 8>, 64, 8);
             else if (helper) code = launch(bign_quad29_kernel<N, 256, 8>, 256, 8);
-#ifdef BEE2HIP_EXPERIMENTS      // reachable only with the helper quad switched off (tune 2): A/B record
-            else if (n <= ((size_t)1 << 13)) code = launch(bign_quad29_kernel<N, 64, 4>, 64, 4);
-#endif
-            else code = launch(bign_quad29_kernel<N, 256, 4>, 256, 4);
+            else code = launch(bign_quad29_kernel<N, 256, 4>, 256, 4);      // (also what 0x43 forces at every size)
         }
         if (code != ERR_OK) return code;
     }
     if (path != 3) {
-        // The MAIN kernel takes its multiply-adds in pairs (VtOpsP, bign_dev.hpp mac2) where that pays -- measured, tools/ab/verify_pairs_ab.py,
+        // The MAIN kernel takes its multiply-adds in pairs (VtOpsP, bign_dev.hpp mac2) where that pays -- measured,
         // profiles/r04_mad_pairs_vt.txt: the 384- / 512-bit curves up to 2^16 signatures (ONE wavefront per SIMD: 2.85 -> 2.14 ms and
         // 6.26 -> 4.82 ms at 2^16), the 256-bit curve from 2^18 on (four wavefronts: +0.8 % at 2^18, +1.7 % at 2^19); at two wavefronts
-        // per SIMD the paired form loses 2-5 % on every curve, and points / prep do not care.  g_verify_pairs: -1 by size, 0 never, else always (A/B).
-        const bool pair_main = g_verify_pairs >= 0 ? g_verify_pairs != 0
-                             : N == 8 ? n >= ((size_t)1 << 18) : n <= ((size_t)1 << 16);
+        // per SIMD the paired form loses 2-5 % on every curve, and points / prep do not care.
+        const bool pair_main = N == 8 ? n >= ((size_t)1 << 18) : n <= ((size_t)1 << 16);
         if constexpr (N != 8)
             hipLaunchKernelGGL((bign_points_kernel<N>), dim3(g256), dim3(256), 0, st, (const uint8_t *)d_hashes,
                                (const uint8_t *)d_sigs, (const uint8_t *)d_pubkeys, n, S);
         hipLaunchKernelGGL((bign_prep_kernel<N>), dim3((unsigned)((plan + 255) / 256)), dim3(256), 0, st,
                            (const uint8_t *)d_hashes, (const uint8_t *)d_sigs, (const uint8_t *)d_pubkeys, n, plan,
                            (int)sp, S);
-        if (ev_prep) B2H_TRY(hipEventRecord(ev_prep, st));
         if constexpr (N == 8) {
             if (path == 2) {
                 const unsigned wg = n <= ((size_t)1 << 14) ? 64u : 256u;
@@ -1773,9 +1724,9 @@ static err_t launch_bign_verify_t(const uint8_t *oid_der, size_t oid_len, const 
     // signature) and a lone wavefront issues at about a third of a SIMD's rate, so fewer, longer lanes cost
     // little until the lanes no longer cover the SIMDs: measured best at 2^18 signatures K = 8 on the 256-bit
     // curve (72 us; K = 2: 105 us) and K = 4 on the wider ones (profiles/r01_bign_ab_inv.txt)
-    // (round 4, tools/ab/inv_lanes_ab.py: with the division-step inversion the optimum is flat; up to 2^17 signatures on the 256-bit curve 2^16
+    // (round 4: with the division-step inversion the optimum is flat; up to 2^17 signatures on the 256-bit curve 2^16
     //  lanes -- one wavefront per SIMD, two signatures each -- are 4-7 % ahead of 2^15; profiles/r04_inv_lanes_ab.txt)
-    const size_t inv_lanes = g_inv_lanes_log2 > 0 ? (size_t)1 << g_inv_lanes_log2 : N == 8 && n > ((size_t)1 << 17) ? 32768 : 65536;
+    const size_t inv_lanes = N == 8 && n > ((size_t)1 << 17) ? 32768 : 65536;
     const size_t k_inv = std::min<size_t>(16, std::max<size_t>(1, n / inv_lanes));
     const size_t lanes = (n + k_inv - 1) / k_inv;
     hipLaunchKernelGGL(bign_inv_kernel<N>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, n, lanes,
@@ -1793,45 +1744,6 @@ static err_t launch_bign_verify_t(const uint8_t *oid_der, size_t oid_len, const 
                            (const uint8_t *)d_sigs, n, S, oid, (uint32_t *)d_codes);
     }
     B2H_TRY(hipGetLastError());
-    return ERR_OK;
-    };   // run_range
-
-    // parts: only the one-lane throughput kernels of a big batch
-    size_t parts = 1;
-    {
-        const bool one_lane = N == 8 ? (g_verify_path == 1 || (g_verify_path == 0 && n_total > ((size_t)1 << 16)))
-                                     : (g_verify_path == 1 || (g_verify_path == 0 && n_total > ((size_t)1 << 15)));
-        // measured (profiles/r03_verify_split.txt): no gain -- 2 parts -1.5 % at 2^18, +-0 at 2^19 / 2^20, 3-4 parts -5..-30 %; the
-        // default is therefore ONE part, and the parts stay reachable through bee2hip_internal_tune(8, parts) for the record
-        if (one_lane) parts = g_verify_split >= 2 ? (size_t)g_verify_split : 1;
-        if (parts > 4) parts = 4;
-        if (n_total < parts * 4096) parts = 1;
-    }
-    if (parts == 1) return run_range(0, n_total, st, nullptr);
-    code = t_aux.get();
-    if (code != ERR_OK) return code;
-    hipEvent_t ev[9];                               // fork, prep done x 4, join x 4
-    for (hipEvent_t &e : ev) e = nullptr;
-    const auto cleanup = [&]() { for (hipEvent_t &e : ev) if (e) (void)hipEventDestroy(e); };
-    for (size_t i = 0; i < 1 + 2 * parts; ++i)
-        if (hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) { cleanup(); return hip_fail(hipGetLastError(), "hipEventCreate"); }
-    const size_t per = ((n_total / parts + 255) / 256) * 256;
-    hipError_t he = hipEventRecord(ev[0], st);       // everything queued so far (inputs, the OID prefix) is before the fork
-    for (size_t p = 0; p < parts && he == hipSuccess && code == ERR_OK; ++p) {
-        const size_t off = p * per, cnt = p + 1 == parts ? n_total - off : per;
-        const hipStream_t sp_ = p == 0 ? st : t_aux.s[p - 1];
-        if (p) {
-            he = hipStreamWaitEvent(sp_, ev[0], 0);
-            if (he == hipSuccess) he = hipStreamWaitEvent(sp_, ev[p], 0);          // the previous part's prep is through
-            if (he != hipSuccess) break;
-        }
-        code = run_range(off, cnt, sp_, ev[1 + p]);
-        if (code == ERR_OK && p) he = hipEventRecord(ev[1 + parts + p], sp_);
-    }
-    for (size_t p = 1; p < parts && he == hipSuccess && code == ERR_OK; ++p) he = hipStreamWaitEvent(st, ev[1 + parts + p], 0);
-    cleanup();                                      // destroying a pending event is allowed: it is released when it completes
-    if (code != ERR_OK) return code;
-    if (he != hipSuccess) return hip_fail(he, "verify parts");
     return ERR_OK;
 }
 
@@ -2220,9 +2132,9 @@ static err_t launch_bign_verify_onekey_t(const uint8_t *oid_der, size_t oid_len,
                            kts[0]->tab, (const uint4 *)nullptr, (const uint32_t *)nullptr, (const uint4 *const *)nullptr, 1u);
     hipLaunchKernelGGL(bign_slow_kernel<N>, dim3(g64), dim3(64), 0, st, dsg, d_keys, n, S, keyed ? ~(size_t)0 : (size_t)0);
     // shared inversions and the hash tail: as launch_bign_verify_t
-    // (round 4, tools/ab/inv_lanes_ab.py: with the division-step inversion the optimum is flat; up to 2^17 signatures on the 256-bit curve 2^16
+    // (round 4: with the division-step inversion the optimum is flat; up to 2^17 signatures on the 256-bit curve 2^16
     //  lanes -- one wavefront per SIMD, two signatures each -- are 4-7 % ahead of 2^15; profiles/r04_inv_lanes_ab.txt)
-    const size_t inv_lanes = g_inv_lanes_log2 > 0 ? (size_t)1 << g_inv_lanes_log2 : N == 8 && n > ((size_t)1 << 17) ? 32768 : 65536;
+    const size_t inv_lanes = N == 8 && n > ((size_t)1 << 17) ? 32768 : 65536;
     const size_t k_inv = std::min<size_t>(16, std::max<size_t>(1, n / inv_lanes));
     const size_t lanes = (n + k_inv - 1) / k_inv;
     hipLaunchKernelGGL(bign_inv_kernel<N>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, n, lanes, (int)k_inv, S);

@@ -147,57 +147,6 @@ __device__ __forceinline__ void proj_madd_complete(projT<N> &P, const affT<N> &Q
 template <int N>
 __device__ __forceinline__ uint32_t proj_to_affine_ct(feT<N> &x, feT<N> &y, const projT<N> &acc);
 
-// -------------------------------------------------------------- k G, affine ---
-// R = k G for a secret k (any N-limb value; the callers have k in {1 .. q - 1}).  gtab8 is the verify path's 8-bit
-// seed table: entry (win, b) = b 2^(8 win) G affine, 2N words, at index win * 256 + b; window w of 4 bits reads
-// its 15 entries j 16^w G = entry (w / 2, j << 4 (w & 1)).
-template <int N>
-__device__ __forceinline__ uint32_t mul_base_ct(feT<N> &x, feT<N> &y, const uint32_t (&k)[N], const uint32_t *__restrict__ gtab8)
-{
-    uint32_t kk[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) kk[i] = k[i];
-    feT<N> b;
-#pragma unroll
-    for (int i = 0; i < N; ++i) b.v[i] = curve_b<N>()[i];
-    projT<N> acc;
-    fe_set_zero(acc.X); fe_set_one(acc.Y); fe_set_zero(acc.Z);          // O
-#pragma unroll 1
-    for (int w = 0; w < 8 * N; ++w) {
-        const uint32_t dg = kk[0] & 15u;
-        // k >>= 4
-#pragma unroll
-        for (int i = 0; i < N - 1; ++i) kk[i] = __builtin_amdgcn_alignbit(kk[i + 1], kk[i], 4);
-        kk[N - 1] >>= 4;
-        // scan the whole row of the table; addresses depend on w only (scalar loads)
-        const uint32_t *row = gtab8 + ((size_t)(w >> 1) * GT8_ENTRIES) * (2 * N);
-        const int sh = 4 * (w & 1);
-        affT<N> E;
-        fe_set_zero(E.x); fe_set_zero(E.y);
-#pragma unroll
-        for (int j = 1; j < 16; ++j) {
-            const uint32_t m = ct_eq_small(dg, (uint32_t)j);
-            const uint32_t *e = row + (size_t)(j << sh) * (2 * N);
-#pragma unroll
-            for (int l = 0; l < N; ++l) {
-                E.x.v[l] = bitop3<0xF8>(E.x.v[l], e[l], m);             // a | (b & c)
-                E.y.v[l] = bitop3<0xF8>(E.y.v[l], e[N + l], m);
-            }
-        }
-        // digit 0: E = (0, 0), not a point -- add it all the same and keep the old accumulator
-        projT<N> sum = acc;
-        proj_madd_complete(sum, E, b);
-        const uint32_t keep = ct_eq_small(dg, 0u);
-#pragma unroll
-        for (int l = 0; l < N; ++l) {
-            acc.X.v[l] = ct_sel(keep, acc.X.v[l], sum.X.v[l]);
-            acc.Y.v[l] = ct_sel(keep, acc.Y.v[l], sum.Y.v[l]);
-            acc.Z.v[l] = ct_sel(keep, acc.Z.v[l], sum.Z.v[l]);
-        }
-    }
-    return proj_to_affine_ct(x, y, acc);
-}
-
 // affine x = X / Z, y = Y / Z of a secret point; all-ones iff the point is O (Z = 0: k = 0 mod q) -- then x = y = 0
 template <int N>
 __device__ __forceinline__ uint32_t proj_to_affine_ct(feT<N> &x, feT<N> &y, const projT<N> &acc)
@@ -255,20 +204,15 @@ __device__ __forceinline__ void jac_madd_ct(jacT<N> &T, const affT<N> &E)
     fe_sub(T.Y, t, S2);                                 // Y3 = r (V - X3) - Y1 H^3
 }
 
-template <int N, bool JAC>
+template <int N>
 __device__ __forceinline__ uint32_t mul_base_ct6(feT<N> &x, feT<N> &y, const uint32_t (&k)[N], const uint32_t *__restrict__ gtab6)
 {
     uint32_t kk[N];
 #pragma unroll
     for (int i = 0; i < N; ++i) kk[i] = k[i];
-    feT<N> b;
-#pragma unroll
-    for (int i = 0; i < N; ++i) b.v[i] = curve_b<N>()[i];
-    projT<N> acc;
-    fe_set_zero(acc.X); fe_set_one(acc.Y); fe_set_zero(acc.Z);          // O
     jacT<N> J;
     fe_set_zero(J.X); fe_set_one(J.Y); fe_set_zero(J.Z);
-    uint32_t at_inf = ~0u;                                              // JAC: all-ones while no non-zero digit has been met
+    uint32_t at_inf = ~0u;                                              // all-ones while no non-zero digit has been met
     feT<N> one;
     fe_set_one(one);
     uint32_t carry = 0;
@@ -300,117 +244,6 @@ __device__ __forceinline__ uint32_t mul_base_ct6(feT<N> &x, feT<N> &y, const uin
 #pragma unroll
         for (int l = 0; l < N; ++l) E.y.v[l] = ct_sel(neg, ny.v[l], E.y.v[l]);
         const uint32_t keep = ct_eq_small(mag, 0u);
-        if constexpr (JAC) {
-            jacT<N> sum = J;
-            jac_madd_ct(sum, E);                                        // digit 0 or accumulator still O: computed, not used
-            const uint32_t set = at_inf & ~keep;                        // first non-zero digit: J <- (x, y, 1)
-#pragma unroll
-            for (int l = 0; l < N; ++l) {
-                J.X.v[l] = ct_sel(keep, J.X.v[l], ct_sel(set, E.x.v[l], sum.X.v[l]));
-                J.Y.v[l] = ct_sel(keep, J.Y.v[l], ct_sel(set, E.y.v[l], sum.Y.v[l]));
-                J.Z.v[l] = ct_sel(keep, J.Z.v[l], ct_sel(set, one.v[l], sum.Z.v[l]));
-            }
-            at_inf &= keep;
-        } else {
-            projT<N> sum = acc;
-            proj_madd_complete(sum, E, b);                              // digit 0: (0, 0) is not a point; the old accumulator is kept
-#pragma unroll
-            for (int l = 0; l < N; ++l) {
-                acc.X.v[l] = ct_sel(keep, acc.X.v[l], sum.X.v[l]);
-                acc.Y.v[l] = ct_sel(keep, acc.Y.v[l], sum.Y.v[l]);
-                acc.Z.v[l] = ct_sel(keep, acc.Z.v[l], sum.Z.v[l]);
-            }
-        }
-    }
-    if constexpr (JAC) {
-        // x = X / Z^2, y = Y / Z^3; Z = 0 (or nothing ever added: k = 0) is the point at infinity
-#pragma unroll
-        for (int l = 0; l < N; ++l) J.Z.v[l] &= ~at_inf;
-        feT<N> zc;
-        fe_canon(zc, J.Z);
-        const feT<N> zi = fe_inv_safegcd<N, true>(zc);
-        feT<N> chk, zi2;
-        fe_mul(chk, zc, zi);
-        fe_canon(chk, chk);
-        chk.v[0] ^= 1u;                                                 // 0 iff Z * Z^-1 == 1
-        fe_sqr(zi2, zi);
-        fe_mul(x, J.X, zi2);
-        fe_mul(zi2, zi2, zi);
-        fe_mul(y, J.Y, zi2);
-        fe_canon(x, x);
-        fe_canon(y, y);
-        const uint32_t inf = ct_is_zero(zc.v) | ~ct_is_zero(chk.v);
-#pragma unroll
-        for (int l = 0; l < N; ++l) { x.v[l] &= ~inf; y.v[l] &= ~inf; }
-        return inf;
-    } else {
-        return proj_to_affine_ct(x, y, acc);
-    }
-}
-
-// ---- the same multiplication with the window's entry LOOKED UP in LDS (round 4) ---------------------------------------------
-// The masked scan above costs one full-rate VALU op per table word per entry: 512 + 96 of the ~3 800 instructions of a
-// window, and it is what kept the windows at 6 bits.  Here the 1024 lanes of a workgroup walk the windows together and the
-// window's row sits in LDS in 32 copies, copy r holding its 64-bit words at byte address (word * 32 + r) * 8: lane l reads
-// words (entry * N + i) of copy l mod 32, i.e. ALWAYS the two banks 2 (l mod 32), 2 (l mod 32) + 1 of the 64
-// (ds_read_b64: lane groups {0-31}, {32-63}, bank = (a / 4) mod 64, MI355X_MICROARCH.md LDS table).  Whatever the secret
-// entry numbers are, the 32 lanes of a group hit 32 disjoint bank pairs: no conflict, the same LDS cycles for every scalar --
-// the argument of the bank-private belt tables (belt_dev.hpp), with SQ_LDS_BANK_CONFLICT = 0 to show for it
-// (profiles/r04_sign_lds.txt).  A row of 2^(WB-1) entries x 8N octets x 32 copies must fit the CU's 160 KiB: signed 7-bit
-// windows on the 256-bit curve (64 entries: 128 KiB, one workgroup of 1024 lanes = 4 wavefronts per SIMD, 37 additions instead
-// of 43).  Per window: barrier, 16 broadcast loads + ds_write_b64 per lane to refill the row (addresses depend on the window
-// and the lane only), barrier, N ds_read_b64 -- ~60 instructions where the scan took ~730.  Digits, negation, the masked
-// Jacobian addition and the schedule argument are those of mul_base_ct6<N, true>: digits t - 128 [t >= 64] in [-64, 63],
-// |A| <= 64 (128^w - 1) / 127 < 128^w before window w, and the top window starts at bit 252 exactly as with 6-bit windows.
-template <int N, int WB>
-__device__ __forceinline__ uint32_t mul_base_ct_lds(feT<N> &x, feT<N> &y, const uint32_t (&k)[N], const uint64_t *__restrict__ tabw,
-                                                    uint64_t *s_row, const int x_only /* public: signing needs x_R alone */)
-{
-    constexpr int W = WinW<N, WB>::W, ENT = WinW<N, WB>::ENT, QW = ENT * N;       // 64-bit words of a row
-    static_assert(QW * 32 % 1024 == 0, "the refill is written for 1024 lanes");
-    const unsigned tid = threadIdx.x, rep = tid & 31u;
-    uint32_t kk[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) kk[i] = k[i];
-    jacT<N> J;
-    fe_set_zero(J.X); fe_set_one(J.Y); fe_set_zero(J.Z);
-    uint32_t at_inf = ~0u;
-    feT<N> one;
-    fe_set_one(one);
-    uint32_t carry = 0;
-#pragma unroll 1
-    for (int w = 0; w < W; ++w) {
-        __syncthreads();                                                // every lane is through with the previous row
-        {
-            const uint64_t *row = tabw + (size_t)w * QW;
-#pragma unroll
-            for (int i = 0; i < QW * 32 / 1024; ++i) {
-                const unsigned q = (tid >> 5) + 32u * i;                // the 32 lanes of a copy-group fetch the same word
-                s_row[q * 32u + rep] = row[q];
-            }
-        }
-        __syncthreads();
-        const uint32_t t = (kk[0] & (uint32_t)(2 * ENT - 1)) + carry;   // 0 .. 2 ENT
-#pragma unroll
-        for (int i = 0; i < N - 1; ++i) kk[i] = __builtin_amdgcn_alignbit(kk[i + 1], kk[i], WB);
-        kk[N - 1] >>= WB;
-        carry = (t + (uint32_t)ENT) >> WB;                              // 1 iff t >= ENT
-        const uint32_t d = t - (carry << WB);                           // two's complement of the digit
-        const uint32_t neg = (uint32_t)((int32_t)d >> 31);
-        const uint32_t mag = (d ^ neg) - neg;                           // 0 .. ENT
-        const uint32_t e = (mag - 1u) & (uint32_t)(ENT - 1);            // digit 0 reads entry ENT: looked up, added, not used
-        affT<N> E;
-#pragma unroll
-        for (int l = 0; l < N / 2; ++l) {
-            const uint64_t vx = s_row[(e * N + l) * 32u + rep], vy = s_row[(e * N + N / 2 + l) * 32u + rep];
-            E.x.v[2 * l] = (uint32_t)vx; E.x.v[2 * l + 1] = (uint32_t)(vx >> 32);
-            E.y.v[2 * l] = (uint32_t)vy; E.y.v[2 * l + 1] = (uint32_t)(vy >> 32);
-        }
-        feT<N> ny;
-        fe_neg(ny, E.y);
-#pragma unroll
-        for (int l = 0; l < N; ++l) E.y.v[l] = ct_sel(neg, ny.v[l], E.y.v[l]);
-        const uint32_t keep = ct_eq_small(mag, 0u);
         jacT<N> sum = J;
         jac_madd_ct(sum, E);                                            // digit 0 or accumulator still O: computed, not used
         const uint32_t set = at_inf & ~keep;                            // first non-zero digit: J <- (x, y, 1)
@@ -434,13 +267,10 @@ __device__ __forceinline__ uint32_t mul_base_ct_lds(feT<N> &x, feT<N> &y, const 
     chk.v[0] ^= 1u;                                                     // 0 iff Z * Z^-1 == 1
     fe_sqr(zi2, zi);
     fe_mul(x, J.X, zi2);
+    fe_mul(zi2, zi2, zi);
+    fe_mul(y, J.Y, zi2);
     fe_canon(x, x);
-    fe_set_zero(y);
-    if (!x_only) {
-        fe_mul(zi2, zi2, zi);
-        fe_mul(y, J.Y, zi2);
-        fe_canon(y, y);
-    }
+    fe_canon(y, y);
     const uint32_t inf = ct_is_zero(zc.v) | ~ct_is_zero(chk.v);
 #pragma unroll
     for (int l = 0; l < N; ++l) { x.v[l] &= ~inf; y.v[l] &= ~inf; }
@@ -621,12 +451,15 @@ void bign_mulbase_coop_kernel(const uint8_t *__restrict__ scalars, size_t n, uin
 #ifndef SIGN_MULBASE_WAVES
 #define SIGN_MULBASE_WAVES 3        // 168 VGPRs, 15 spilled: +2.2 % over 2 (186 VGPRs); 4 (128 VGPRs, 110-124 spilled): -31 %
 #endif
-template <int N, int FORM = 0>          // FORM 0: 4-bit windows, 1: signed 6-bit + complete additions, 2: + Jacobian
+// FORM 2: signed 6-bit windows, Jacobian mixed additions (FORM 0 = 4-bit windows and FORM 1 = complete additions are retired,
+// profiles/r03_sign_coop.txt)
+template <int N, int FORM>
 __global__ __launch_bounds__(256, (N == 8 ? SIGN_MULBASE_WAVES : 1))
 void bign_mulbase_ct_kernel(const uint8_t *__restrict__ scalars, size_t n, uint32_t *__restrict__ codes,
-                            uint8_t *__restrict__ xy_out, const uint32_t *__restrict__ gtab8,      // FORM > 0: the signed 6-bit table
+                            uint8_t *__restrict__ xy_out, const uint32_t *__restrict__ gtab6,      // the signed 6-bit table
                             const int MODE, const int X_ONLY)                                      // launch arguments: public, uniform
 {
+    static_assert(FORM == 2, "the product form");
     constexpr int NO = 4 * N;
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
@@ -639,9 +472,7 @@ void bign_mulbase_ct_kernel(const uint8_t *__restrict__ scalars, size_t n, uint3
     }
     feT<N> x, y;
     uint32_t inf;
-    if constexpr (FORM == 2) inf = mul_base_ct6<N, true>(x, y, k, gtab8);
-    else if constexpr (FORM == 1) inf = mul_base_ct6<N, false>(x, y, k, gtab8);
-    else inf = mul_base_ct(x, y, k, gtab8);
+    inf = mul_base_ct6<N>(x, y, k, gtab6);
     if (MODE == 2) {
         valid = ~inf;
         codes[idx] = ct_sel(inf, (uint32_t)ERR_BAD_PARAMS, (uint32_t)ERR_OK);
@@ -655,12 +486,33 @@ void bign_mulbase_ct_kernel(const uint8_t *__restrict__ scalars, size_t n, uint3
     }
 }
 
-// (round 6) The same window walk with the accumulator on nine signed 29-bit limbs (bign_fe29.hpp): the Jacobian mixed addition is
+// ---- the same multiplication with the window's entry LOOKED UP in LDS (round 4) ---------------------------------------------
+// The masked scan above costs one full-rate VALU op per table word per entry: 512 + 96 of the ~3 800 instructions of a
+// window, and it is what kept the windows at 6 bits.  Here the 1024 lanes of a workgroup walk the windows together and the
+// window's row sits in LDS in 32 copies, copy r holding its 64-bit words at byte address (word * 32 + r) * 8: lane l reads
+// words (entry * N + i) of copy l mod 32, i.e. ALWAYS the two banks 2 (l mod 32), 2 (l mod 32) + 1 of the 64
+// (ds_read_b64: lane groups {0-31}, {32-63}, bank = (a / 4) mod 64, MI355X_MICROARCH.md LDS table).  Whatever the secret
+// entry numbers are, the 32 lanes of a group hit 32 disjoint bank pairs: no conflict, the same LDS cycles for every scalar --
+// the argument of the bank-private belt tables (belt_dev.hpp), with SQ_LDS_BANK_CONFLICT = 0 to show for it
+// (profiles/r04_sign_lds.txt).  Per window: barrier, broadcast loads + LDS writes per lane to refill the row (addresses
+// depend on the window and the lane only), barrier, the look-up -- ~60 instructions where the scan took ~730.  Digits,
+// negation, the masked Jacobian addition and the schedule argument are those of mul_base_ct6<N>.  That first form (signed
+// 7-bit windows in 32 copies of 64-bit words, 128 KiB) is retired; the product takes 8-bit windows in 16 copies:
+//
+// Signed 8-bit windows (33 additions on the 256-bit curve): 128 entries x 64 octets = 8 KiB per row, which fits LDS in SIXTEEN
+// copies of 16-octet words, copy r at byte address (word * 16 + r) * 16, read with ds_read_b128 by lane l from copy l mod 16.
+// ds_read_b128 is served in four groups of 16 lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32
+// (MI355X_MICROARCH.md, LDS table) -- and within each of them l mod 16 takes every value once (also within plain runs of 16
+// lanes), so the 16 lanes of a group read 16 disjoint 16-octet slots = all 64 banks once, whatever their entries: no
+// conflict, SQ_LDS_BANK_CONFLICT = 0 for every key class (profiles/r04_sign_lds.txt).  Four reads per look-up.
+// WGL = lanes of the workgroup (1024, or 512 for batches that would leave CUs empty otherwise: two wavefronts per SIMD still reach
+// ~95 % of the multiply-add rate, DESIGN.md 2).
+// (round 6) The accumulator lives on nine signed 29-bit limbs (bign_fe29.hpp): the Jacobian mixed addition is
 // 8 multiplications + 3 squarings, each ONE asm block of 135 / 99 instructions with no carry flags, against ~190 / ~150 VALU
 // instructions (a third of them v_addc_co and v_mov) of the 32-bit product-scanning code -- per window 9 400 -> ~6 900 VALU cycles
-// (profiles/r06_sign_l29_ab.txt).  Constant-time as before: the limb arithmetic is masks, shifts and multiply-adds, the digit's
-// entry is looked up in the bank-private LDS copies, sign and "keep" are applied by ct_sel.  The table stays in 32-bit words
-// (converted on load: 2 instructions per limb); the result goes back to words for the fixed-count inversion.
+// (profiles/r06_sign_l29_ab.txt; the 32-bit form is retired).  Constant-time as before: the limb arithmetic is masks, shifts and
+// multiply-adds, the digit's entry is looked up in the bank-private LDS copies, sign and "keep" are applied by ct_sel.  The table
+// stays in 32-bit words (converted on load: 2 instructions per limb); the result goes back to words for the fixed-count inversion.
 template <int WB, int WGL>
 __device__ __forceinline__ uint32_t mul_base_ct_lds16_l29(feT<8> &x, feT<8> &y, const uint32_t (&k)[8], const uint4 *__restrict__ tabw,
                                                           uint4 *s_row, const int x_only)
@@ -801,224 +653,15 @@ __device__ __forceinline__ uint32_t mul_base_ct_lds16_l29(feT<8> &x, feT<8> &y, 
     return inf;
 }
 
-// Signed 8-bit windows (33 additions on the 256-bit curve): 128 entries x 64 octets = 8 KiB per row, which fits LDS in SIXTEEN
-// copies of 16-octet words, copy r at byte address (word * 16 + r) * 16, read with ds_read_b128 by lane l from copy l mod 16.
-// ds_read_b128 is served in four groups of 16 lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32
-// (MI355X_MICROARCH.md, LDS table) -- and within each of them l mod 16 takes every value once (also within plain runs of 16
-// lanes), so the 16 lanes of a group read 16 disjoint 16-octet slots = all 64 banks once, whatever their entries: no
-// conflict, SQ_LDS_BANK_CONFLICT = 0 for every key class (profiles/r04_sign_lds.txt).  Four reads per look-up.
-// WGL = lanes of the workgroup (1024, or 512 for batches that would leave CUs empty otherwise: two wavefronts per SIMD still reach
-// ~95 % of the multiply-add rate, DESIGN.md 2).
-template <int N, int WB, int WGL>
-__device__ __forceinline__ uint32_t mul_base_ct_lds16(feT<N> &x, feT<N> &y, const uint32_t (&k)[N], const uint4 *__restrict__ tabw,
-                                                      uint4 *s_row, const int x_only)
-{
-    constexpr int W = WinW<N, WB>::W, ENT = WinW<N, WB>::ENT, OW = ENT * N / 2;     // 16-octet words of a row
-    static_assert(OW * 16 % WGL == 0 && N % 4 == 0 && WGL % 16 == 0, "the refill covers the row with whole passes of the workgroup");
-    const unsigned tid = threadIdx.x, rep = tid & 15u;
-    uint32_t kk[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) kk[i] = k[i];
-    jacT<N> J;
-    fe_set_zero(J.X); fe_set_one(J.Y); fe_set_zero(J.Z);
-    uint32_t at_inf = ~0u;
-    feT<N> one;
-    fe_set_one(one);
-    uint32_t carry = 0;
-#pragma unroll 1
-    for (int w = 0; w < W; ++w) {
-        __syncthreads();
-        {
-            const uint4 *row = tabw + (size_t)w * OW;
-#pragma unroll
-            for (int i = 0; i < OW * 16 / WGL; ++i) {
-                const unsigned q = (tid >> 4) + (unsigned)(WGL / 16) * i;   // the 16 lanes of a copy-group fetch the same word
-                s_row[q * 16u + rep] = row[q];
-            }
-        }
-        __syncthreads();
-        const uint32_t t = (kk[0] & (uint32_t)(2 * ENT - 1)) + carry;   // 0 .. 2 ENT
-#pragma unroll
-        for (int i = 0; i < N - 1; ++i) kk[i] = __builtin_amdgcn_alignbit(kk[i + 1], kk[i], WB);
-        kk[N - 1] >>= WB;
-        carry = (t + (uint32_t)ENT) >> WB;
-        const uint32_t d = t - (carry << WB);
-        const uint32_t neg = (uint32_t)((int32_t)d >> 31);
-        const uint32_t mag = (d ^ neg) - neg;                           // 0 .. ENT
-        const uint32_t e = (mag - 1u) & (uint32_t)(ENT - 1);            // digit 0 reads entry ENT: looked up, added, not used
-        affT<N> E;
-#pragma unroll
-        for (int l = 0; l < N / 4; ++l) {
-            const uint4 vx = s_row[(e * (N / 2) + l) * 16u + rep], vy = s_row[(e * (N / 2) + N / 4 + l) * 16u + rep];
-            E.x.v[4 * l] = vx.x; E.x.v[4 * l + 1] = vx.y; E.x.v[4 * l + 2] = vx.z; E.x.v[4 * l + 3] = vx.w;
-            E.y.v[4 * l] = vy.x; E.y.v[4 * l + 1] = vy.y; E.y.v[4 * l + 2] = vy.z; E.y.v[4 * l + 3] = vy.w;
-        }
-        feT<N> ny;
-        fe_neg(ny, E.y);
-#pragma unroll
-        for (int l = 0; l < N; ++l) E.y.v[l] = ct_sel(neg, ny.v[l], E.y.v[l]);
-        const uint32_t keep = ct_eq_small(mag, 0u);
-        jacT<N> sum = J;
-        jac_madd_ct(sum, E);
-        const uint32_t set = at_inf & ~keep;
-#pragma unroll
-        for (int l = 0; l < N; ++l) {
-            J.X.v[l] = ct_sel(keep, J.X.v[l], ct_sel(set, E.x.v[l], sum.X.v[l]));
-            J.Y.v[l] = ct_sel(keep, J.Y.v[l], ct_sel(set, E.y.v[l], sum.Y.v[l]));
-            J.Z.v[l] = ct_sel(keep, J.Z.v[l], ct_sel(set, one.v[l], sum.Z.v[l]));
-        }
-        at_inf &= keep;
-    }
-#pragma unroll
-    for (int l = 0; l < N; ++l) J.Z.v[l] &= ~at_inf;
-    feT<N> zc;
-    fe_canon(zc, J.Z);
-    const feT<N> zi = fe_inv_safegcd<N, true>(zc);
-    feT<N> chk, zi2;
-    fe_mul(chk, zc, zi);
-    fe_canon(chk, chk);
-    chk.v[0] ^= 1u;
-    fe_sqr(zi2, zi);
-    fe_mul(x, J.X, zi2);
-    fe_canon(x, x);
-    fe_set_zero(y);
-    if (!x_only) {
-        fe_mul(zi2, zi2, zi);
-        fe_mul(y, J.Y, zi2);
-        fe_canon(y, y);
-    }
-    const uint32_t inf = ct_is_zero(zc.v) | ~ct_is_zero(chk.v);
-#pragma unroll
-    for (int l = 0; l < N; ++l) { x.v[l] &= ~inf; y.v[l] &= ~inf; }
-    return inf;
-}
-
-// The same walk with the accumulator in "XYZZ" coordinates (X, Y, ZZ = Z^2, ZZZ = Z^3; x = X / ZZ, y = Y / ZZZ): the mixed addition
-// is 8M + 2S instead of 8M + 3S (no Z^2 to recompute) for one more coordinate to carry -- U2 = x2 ZZ1, S2 = y2 ZZZ1, P = U2 - X1,
-// R = S2 - Y1, PP = P^2, PPP = P PP, Q = X1 PP, X3 = R^2 - PPP - 2Q, Y3 = R (Q - X3) - Y1 PPP, ZZ3 = ZZ1 PP, ZZZ3 = ZZZ1 PPP
-// (the same group operation with the same exceptional cases as jac_madd_ct: P = 0, excluded by the schedule).  To keep the
-// working set inside 128 VGPRs the selected entry is NOT held across the addition: the row is still in LDS when the new
-// coordinates are blended in, so the "first non-zero digit" case reads it again (8 more ds_read_b64).
-template <int N, int WB>
-__device__ __forceinline__ uint32_t mul_base_ct_lds_xyzz(feT<N> &x, feT<N> &y, const uint32_t (&k)[N], const uint64_t *__restrict__ tabw,
-                                                         uint64_t *s_row, const int x_only)
-{
-    constexpr int W = WinW<N, WB>::W, ENT = WinW<N, WB>::ENT, QW = ENT * N;
-    static_assert(QW * 32 % 1024 == 0, "the refill is written for 1024 lanes");
-    const unsigned tid = threadIdx.x, rep = tid & 31u;
-    uint32_t kk[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) kk[i] = k[i];
-    feT<N> X, Y, ZZ, ZZZ;
-    fe_set_zero(X); fe_set_one(Y); fe_set_zero(ZZ); fe_set_zero(ZZZ);
-    uint32_t at_inf = ~0u, carry = 0;
-    const auto read_entry = [&](affT<N> &E, uint32_t e, uint32_t neg) {
-#pragma unroll
-        for (int l = 0; l < N / 2; ++l) {
-            const uint64_t vx = s_row[(e * N + l) * 32u + rep], vy = s_row[(e * N + N / 2 + l) * 32u + rep];
-            E.x.v[2 * l] = (uint32_t)vx; E.x.v[2 * l + 1] = (uint32_t)(vx >> 32);
-            E.y.v[2 * l] = (uint32_t)vy; E.y.v[2 * l + 1] = (uint32_t)(vy >> 32);
-        }
-        feT<N> ny;
-        fe_neg(ny, E.y);
-#pragma unroll
-        for (int l = 0; l < N; ++l) E.y.v[l] = ct_sel(neg, ny.v[l], E.y.v[l]);
-    };
-#pragma unroll 1
-    for (int w = 0; w < W; ++w) {
-        __syncthreads();
-        {
-            const uint64_t *row = tabw + (size_t)w * QW;
-#pragma unroll
-            for (int i = 0; i < QW * 32 / 1024; ++i) {
-                const unsigned q = (tid >> 5) + 32u * i;
-                s_row[q * 32u + rep] = row[q];
-            }
-        }
-        __syncthreads();
-        const uint32_t t = (kk[0] & (uint32_t)(2 * ENT - 1)) + carry;
-#pragma unroll
-        for (int i = 0; i < N - 1; ++i) kk[i] = __builtin_amdgcn_alignbit(kk[i + 1], kk[i], WB);
-        kk[N - 1] >>= WB;
-        carry = (t + (uint32_t)ENT) >> WB;
-        const uint32_t d = t - (carry << WB);
-        const uint32_t neg = (uint32_t)((int32_t)d >> 31);
-        const uint32_t mag = (d ^ neg) - neg;
-        const uint32_t e = (mag - 1u) & (uint32_t)(ENT - 1);
-        const uint32_t keep = ct_eq_small(mag, 0u);
-        const uint32_t set = at_inf & ~keep;
-        feT<N> nX, nY, nZZ, nZZZ;
-        {
-            feT<N> P, R, PP, PPP, Q, t0, t1;
-            {
-                affT<N> E;
-                read_entry(E, e, neg);
-                fe_mul(P, E.x, ZZ);                                     // U2
-                fe_mul(R, E.y, ZZZ);                                    // S2
-            }
-            fe_sub(P, P, X);
-            fe_sub(R, R, Y);
-            fe_sqr(PP, P);
-            fe_mul(PPP, P, PP);
-            fe_mul(Q, X, PP);
-            fe_mul(nZZ, ZZ, PP);
-            fe_mul(nZZZ, ZZZ, PPP);
-            fe_sqr(t0, R);
-            fe_sub(t0, t0, PPP);
-            fe_dbl(t1, Q);
-            fe_sub(nX, t0, t1);
-            fe_sub(t0, Q, nX);
-            fe_mul(t0, R, t0);
-            fe_mul(t1, Y, PPP);
-            fe_sub(nY, t0, t1);
-        }
-        {
-            affT<N> E;                                                  // again, for the lanes whose accumulator starts here
-            read_entry(E, e, neg);
-#pragma unroll
-            for (int l = 0; l < N; ++l) {
-                const uint32_t o = l == 0 ? 1u : 0u;
-                X.v[l] = ct_sel(keep, X.v[l], ct_sel(set, E.x.v[l], nX.v[l]));
-                Y.v[l] = ct_sel(keep, Y.v[l], ct_sel(set, E.y.v[l], nY.v[l]));
-                ZZ.v[l] = ct_sel(keep, ZZ.v[l], ct_sel(set, o, nZZ.v[l]));
-                ZZZ.v[l] = ct_sel(keep, ZZZ.v[l], ct_sel(set, o, nZZZ.v[l]));
-            }
-        }
-        at_inf &= keep;
-    }
-#pragma unroll
-    for (int l = 0; l < N; ++l) ZZ.v[l] &= ~at_inf;
-    feT<N> zc;
-    fe_canon(zc, ZZ);
-    const feT<N> zi = fe_inv_safegcd<N, true>(zc);
-    feT<N> chk;
-    fe_mul(chk, zc, zi);
-    fe_canon(chk, chk);
-    chk.v[0] ^= 1u;                                                     // 0 iff ZZ * ZZ^-1 == 1
-    fe_mul(x, X, zi);
-    fe_canon(x, x);
-    fe_set_zero(y);
-    if (!x_only) {                                                      // 1 / ZZZ = ZZZ / ZZ^3 (ZZZ^2 = ZZ^3)
-        feT<N> z2, z3;
-        fe_sqr(z2, zi);
-        fe_mul(z3, z2, zi);
-        fe_mul(y, Y, ZZZ);
-        fe_mul(y, y, z3);
-        fe_canon(y, y);
-    }
-    const uint32_t inf = ct_is_zero(zc.v) | ~ct_is_zero(chk.v);
-#pragma unroll
-    for (int l = 0; l < N; ++l) { x.v[l] &= ~inf; y.v[l] &= ~inf; }
-    return inf;
-}
-
-// the LDS look-up form: modes and outputs as bign_mulbase_ct_kernel; blocks of 1024 lanes, all of which walk the windows
-// (a lane beyond n multiplies by 0 and writes nothing: the barriers need every lane)
-template <int N, int WB, bool XYZZ, int WGL = 1024, bool L29 = (N == 8 && WB == 8)>
+// the LDS look-up form: modes and outputs as bign_mulbase_ct_kernel; blocks of WGL lanes, all of which walk the windows
+// (a lane beyond n multiplies by 0 and writes nothing: the barriers need every lane).  256-bit curve, signed 8-bit windows,
+// 29-bit limbs: the 7-bit windows (WB = 7), their XYZZ accumulator and the 32-bit limbs (L29 = false) are retired.
+template <int N, int WB, bool XYZZ, int WGL = 1024, bool L29 = true>
 __global__ __launch_bounds__(WGL)
 void bign_mulbase_lds_kernel(const uint8_t *__restrict__ scalars, size_t n, uint32_t *__restrict__ codes,
                              uint8_t *__restrict__ xy_out, const uint64_t *__restrict__ tabw, const int MODE, const int X_ONLY)
 {
+    static_assert(N == 8 && WB == 8 && !XYZZ && L29, "the product form");
     constexpr int NO = 4 * N;
     extern __shared__ __attribute__((aligned(16))) uint64_t s_row_dyn[];
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1031,12 +674,7 @@ void bign_mulbase_lds_kernel(const uint8_t *__restrict__ scalars, size_t n, uint
     if (MODE == 1) valid = ct_in_range_q(k);
     feT<N> x, y;
     uint32_t inf;
-    if constexpr (WB == 8 && L29)
-        inf = mul_base_ct_lds16_l29<WB, WGL>(x, y, k, reinterpret_cast<const uint4 *>(tabw), reinterpret_cast<uint4 *>(s_row_dyn), X_ONLY);
-    else if constexpr (WB == 8)
-        inf = mul_base_ct_lds16<N, WB, WGL>(x, y, k, reinterpret_cast<const uint4 *>(tabw), reinterpret_cast<uint4 *>(s_row_dyn), X_ONLY);
-    else if constexpr (XYZZ) inf = mul_base_ct_lds_xyzz<N, WB>(x, y, k, tabw, s_row_dyn, X_ONLY);
-    else inf = mul_base_ct_lds<N, WB>(x, y, k, tabw, s_row_dyn, X_ONLY);
+    inf = mul_base_ct_lds16_l29<WB, WGL>(x, y, k, reinterpret_cast<const uint4 *>(tabw), reinterpret_cast<uint4 *>(s_row_dyn), X_ONLY);
     if (!live) return;
     if (MODE == 1) codes[idx] = ct_sel(valid, (uint32_t)ERR_OK, ERR_BAD_PRIVKEY_V);
     if (MODE == 2) {
@@ -1384,78 +1022,50 @@ static err_t sign_scratch(hipStream_t st, size_t n, SignScratch &S)
 }
 
 // k G by one lane per scalar (throughput) or by 64 / 16 / 4 lanes per scalar (latency; each form fills the device -- one
-// wavefront per SIMD -- at 2^10 / 2^12 / 2^14 scalars).  g_sign_lanes: 0 = by batch size; 1 / 102 / 101 = always one lane
-// (signed 6-bit windows with Jacobian mixed additions / with complete additions / unsigned 4-bit windows), 4 / 16 / 64 forced
-// (bee2hip_internal_tune 10).  tools/ab/sign_coop_ab.py measures all six at every size on the three curves
-// (profiles/r03_sign_coop.txt): 64 lanes up to 2^10 scalars, 16 up to 2^13, 4 up to 2^15, one lane above.
+// wavefront per SIMD -- at 2^10 / 2^12 / 2^14 scalars).  g_sign_lanes: 0 = by batch size; 1 = one lane (signed 6-bit windows,
+// Jacobian mixed additions), 4 / 16 / 64 = that many lanes, 8 = the LDS look-up form (256-bit curve; elsewhere by size) --
+// forced by bee2hip_internal_tune 10.  profiles/r03_sign_coop.txt measures the forms at every size on the three curves:
+// 64 lanes up to 2^10 scalars, 16 up to 2^13, 4 up to 2^15, one lane above.
 static int g_sign_lanes = 0;
 void set_sign_coop(int v) { g_sign_lanes = v; }
-// (round 4) 8 / 7 = one lane per scalar with the window's entry looked up in LDS (bign_mulbase_lds_kernel: 256-bit curve only,
-// workgroups of 1024 lanes; signed 8-bit windows and 16 copies of the row -- the product -- or signed 7-bit windows and 32
-// copies): from 3 * 2^16 scalars on, where its one round of <= 256 workgroups (0.63 ms) beats the scanning kernel's 256-lane
-// blocks (0.55 ms at 2^17, 0.97 ms at 2^18: tools/ab/sign_lds_ab.py)
+// (round 4) 8 = one lane per scalar with the window's entry looked up in LDS (bign_mulbase_lds_kernel: 256-bit curve only,
+// signed 8-bit windows and 16 copies of the row): from 3 * 2^16 scalars on, where its one round of <= 256 workgroups (0.63 ms)
+// beats the scanning kernel's 256-lane blocks (0.55 ms at 2^17, 0.97 ms at 2^18: profiles/r04_sign_lds.txt)
 constexpr size_t MULBASE_LDS_MIN = (size_t)1 << 15, MULBASE_LDS_512_MAX = (size_t)1 << 17;   // (512-lane workgroups; round 6: from 2^15 scalars -- the 29-bit form with the shared inversion
 //  takes 0.27 | 0.35 ms (key | signature) for anything up to 2^17, the 4-lane cooperative form 0.35 | 0.43 ms at 2^15: profiles/r06_sign_l29_ab.txt)
-constexpr bool LDS_XYZZ = false;       // accumulator of the 7-bit LDS form: Jacobian (8M + 3S).  XYZZ (8M + 2S, one more coordinate) measured: +-0 % (profiles/r04_sign_lds.txt)
 template <int N>
 static inline int mulbase_lanes(size_t n)
 {
-    if (g_sign_lanes == 1 || g_sign_lanes == 4 || g_sign_lanes == 16 || g_sign_lanes == 64 || g_sign_lanes == 101 || g_sign_lanes == 102)
-        return g_sign_lanes;
-    if (N == 8 && (g_sign_lanes == 72 || g_sign_lanes == 7)) return g_sign_lanes;
+    if (g_sign_lanes == 1 || g_sign_lanes == 4 || g_sign_lanes == 16 || g_sign_lanes == 64) return g_sign_lanes;
     if (N == 8 && (g_sign_lanes == 8 || (g_sign_lanes == 0 && n >= MULBASE_LDS_MIN))) return 8;
-#ifdef BEE2HIP_EXPERIMENTS
-    if (N == 8 && g_sign_lanes == 81) return 81;            // the LDS look-up form on 32-bit limbs (round 4-5): A/B record against the 29-bit one
-#endif
     return n <= ((size_t)1 << 10) ? 64 : n <= ((size_t)1 << 13) ? 16 : n <= ((size_t)1 << 15) ? 4 : 1;
 }
-// the table the chosen form reads: the signed 7-bit one for form 7, the signed 6-bit one otherwise (`tab6` of launch_mulbase)
+// the table the chosen form reads: the signed 8-bit one for form 8, the signed 6-bit one otherwise (`tab6` of launch_mulbase)
 template <int N>
 static err_t mulbase_tables(int lanes, const uint32_t **tab, const uint32_t **tabw, hipStream_t st)
 {
     err_t code = bign_table6<N>(tab, tabw, st);
-    if (code == ERR_OK && (lanes == 7 || lanes == 72 || lanes == 8 || lanes == 81)) {
-        if constexpr (N != 8) return ERR_BAD_INPUT;                      // (never: mulbase_lanes picks these forms on the 256-bit curve only)
-        else {
-#ifdef BEE2HIP_EXPERIMENTS
-        code = lanes == 8 || lanes == 81 ? bign_tablew<N, 8>(tabw, st) : bign_tablew<N, 7>(tabw, st);
-#else
-        code = bign_tablew<N, 8>(tabw, st);
-#endif
-        }
+    if (code == ERR_OK && lanes == 8) {
+        if constexpr (N != 8) return ERR_BAD_INPUT;                      // (never: mulbase_lanes picks this form on the 256-bit curve only)
+        else code = bign_tablew<N, 8>(tabw, st);
         if (code == ERR_OK) {
             static std::once_flag once[64];
             hipError_t e = hipSuccess;
             std::call_once(once[cur_dev() & 63], [&] {
-                const int bytes = (int)((size_t)WinW<8, 7>::ENT * 8 * 32 * 8);          // = 128 entries x 64 octets x 16 copies too
+                const int bytes = (int)((size_t)WinW<8, 8>::ENT * 8 * 16 * 8);          // 128 entries x 64 octets x 16 copies
                 e = hipFuncSetAttribute(reinterpret_cast<const void *>(bign_mulbase_lds_kernel<8, 8, false>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
                 if (e == hipSuccess)
                     e = hipFuncSetAttribute(reinterpret_cast<const void *>(bign_mulbase_lds_kernel<8, 8, false, 512>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-#ifdef BEE2HIP_EXPERIMENTS
-                if (e == hipSuccess)
-                    e = hipFuncSetAttribute(reinterpret_cast<const void *>(bign_mulbase_lds_kernel<8, 8, false, 1024, false>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-                if (e == hipSuccess)
-                    e = hipFuncSetAttribute(reinterpret_cast<const void *>(bign_mulbase_lds_kernel<8, 8, false, 512, false>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-                if (e == hipSuccess)
-                    e = hipFuncSetAttribute(reinterpret_cast<const void *>(bign_mulbase_lds_kernel<8, 7, LDS_XYZZ>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-                if (e == hipSuccess)
-                    e = hipFuncSetAttribute(reinterpret_cast<const void *>(bign_mulbase_lds_kernel<8, 7, !LDS_XYZZ>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-#endif
             });
             if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(bign_mulbase_lds_kernel)");
         }
     }
     return code;
 }
-// lanes: 64 / 16 / 4 = cooperative forms on the 4-bit windows of the seed table; 1 = one lane per scalar, signed 6-bit windows
-// (tab6), Jacobian mixed additions; 102 = the same windows with complete additions; 101 = one lane per scalar on the 4-bit
-// windows (the round-2 kernel) -- the last two kept for A/B and as second opinions in the tests
+// lanes: 64 / 16 / 4 = cooperative forms on the 4-bit windows of the seed table; 8 = the LDS look-up form; 1 = one lane per
+// scalar, signed 6-bit windows (tab6), Jacobian mixed additions
 template <int N, int MODE, bool X_ONLY>
 static void launch_mulbase(int lanes, const uint8_t *scalars, size_t n, uint32_t *codes, uint8_t *out, const uint32_t *tab,
                            const uint32_t *tab6, hipStream_t st)
@@ -1464,25 +1074,6 @@ static void launch_mulbase(int lanes, const uint8_t *scalars, size_t n, uint32_t
     if (lanes == 64 || lanes == 16 || lanes == 4)
         hipLaunchKernelGGL((bign_mulbase_coop_kernel<N>), dim3((unsigned)((n * (size_t)lanes + 63) / 64)), dim3(64), 0, st, scalars, n,
                            codes, out, tab, MODE, (int)X_ONLY, lanes);
-#ifdef BEE2HIP_EXPERIMENTS      // second opinions of the tests and the A/B record (tools/ab/sign_coop_ab.py)
-    else if (lanes == 101)
-        hipLaunchKernelGGL((bign_mulbase_ct_kernel<N, 0>), g256, dim3(256), 0, st, scalars, n, codes, out, tab, MODE, (int)X_ONLY);
-    else if (lanes == 102)
-        hipLaunchKernelGGL((bign_mulbase_ct_kernel<N, 1>), g256, dim3(256), 0, st, scalars, n, codes, out, tab6, MODE, (int)X_ONLY);
-#endif
-#ifdef BEE2HIP_EXPERIMENTS
-    else if (lanes == 81) {
-        if constexpr (N == 8) {
-            constexpr size_t lds = (size_t)WinW<N, 8>::ENT * N * 8 * 16;
-            if (n <= MULBASE_LDS_512_MAX)
-                hipLaunchKernelGGL((bign_mulbase_lds_kernel<N, 8, false, 512, false>), dim3((unsigned)((n + 511) / 512)), dim3(512), lds, st, scalars,
-                                   n, codes, out, reinterpret_cast<const uint64_t *>(tab6), MODE, (int)X_ONLY);
-            else
-                hipLaunchKernelGGL((bign_mulbase_lds_kernel<N, 8, false, 1024, false>), dim3((unsigned)((n + 1023) / 1024)), dim3(1024), lds, st, scalars, n,
-                                   codes, out, reinterpret_cast<const uint64_t *>(tab6), MODE, (int)X_ONLY);
-        }
-    }
-#endif
     else if (lanes == 8) {
         // signed 8-bit windows, 16 copies of the row read with ds_read_b128 (tab6 = the 8-bit window table): 33 additions
         if constexpr (N == 8) {
@@ -1494,22 +1085,6 @@ static void launch_mulbase(int lanes, const uint8_t *scalars, size_t n, uint32_t
             else
                 hipLaunchKernelGGL((bign_mulbase_lds_kernel<N, 8, false>), dim3((unsigned)((n + 1023) / 1024)), dim3(1024), lds, st, scalars, n,
                                    codes, out, reinterpret_cast<const uint64_t *>(tab6), MODE, (int)X_ONLY);
-        }
-    }
-    else if (lanes == 7 || lanes == 72) {
-        // 256-bit curve, batches that give every CU a workgroup of 1024 lanes: signed 7-bit windows looked up in LDS (tab6 = that table)
-        if constexpr (N == 8) {
-            constexpr size_t lds = (size_t)WinW<N, 7>::ENT * N * 32 * 8;
-            const dim3 g((unsigned)((n + 1023) / 1024));
-            (void)lds; (void)g;
-#ifdef BEE2HIP_EXPERIMENTS      // the 7-bit forms: A/B record and second opinions in the tests
-            if (lanes == 7)
-                hipLaunchKernelGGL((bign_mulbase_lds_kernel<N, 7, LDS_XYZZ>), g, dim3(1024), lds, st, scalars, n, codes, out,
-                                   reinterpret_cast<const uint64_t *>(tab6), MODE, (int)X_ONLY);
-            else
-                hipLaunchKernelGGL((bign_mulbase_lds_kernel<N, 7, !LDS_XYZZ>), g, dim3(1024), lds, st, scalars, n, codes, out,
-                                   reinterpret_cast<const uint64_t *>(tab6), MODE, (int)X_ONLY);
-#endif
         }
     }
     else
@@ -1535,14 +1110,11 @@ static err_t launch_bign_pubkey_calc_t(bool keygen, const void *d_privkeys, size
 static inline uint32_t sign_row_words(size_t msg_octets) { return (uint32_t)((msg_octets + 31) / 32 * 8) | 1u; }
 // lanes per workgroup (one 64 KiB table each): big batches take the largest that fits the CU's 160 KiB with its rows
 // (256-bit curve, no t: 1024 lanes for the nonce, 512 for the tail -- 4 and 2 wavefronts per SIMD where it used to be 1)
-static int g_sign_wg = 0;                                  // bee2hip_internal_tune 12: 0 = by size, 256 / 512 / 1024 = upper bound
-void set_sign_wg(int v) { g_sign_wg = v; }
 static inline int sign_wg(size_t n, uint32_t row_words)
 {
-    // ... as long as every CU still gets a workgroup: 2^16 signatures in 64 workgroups of 1024 lose 8 % (tools/ab/sign_wg_ab.py)
+    // ... as long as every CU still gets a workgroup: 2^16 signatures in 64 workgroups of 1024 lose 8 % (profiles/r03_sign_wg.txt)
     if (n < ((size_t)1 << 17)) return SIGN_WG;
-    const int fit = n < ((size_t)1 << 18) ? 512 : 1024;
-    const int cap = g_sign_wg == 256 || g_sign_wg == 512 || g_sign_wg == 1024 ? (g_sign_wg < fit ? g_sign_wg : fit) : fit;
+    const int cap = n < ((size_t)1 << 18) ? 512 : 1024;
     for (int wg = cap; wg > SIGN_WG; wg >>= 1)
         if (BeltTabTwo::kBytes + (size_t)wg * row_words * 4 <= (size_t)160 * 1024) return wg;
     return SIGN_WG;

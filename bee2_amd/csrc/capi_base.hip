@@ -50,7 +50,7 @@ try {
     err_t code = s.need(n * 192);
     if (code != ERR_OK) return code;
     if (n * 192 >= DUPLEX_MIN)              // chunks of 2^16 states = 12 MiB: upload, permute and download overlap
-        return duplex_inplace(states, (octet *)s.p, 192, n, (size_t)1 << g_duplex_log2_states,
+        return duplex_inplace(states, (octet *)s.p, 192, n, (size_t)1 << DUPLEX_LOG2_STATES,
                               [](octet *d, size_t, size_t cnt, hipStream_t st) { return launch_bashF_batch(d, cnt, st); });
     B2H_TRY(h2d(s.p, states, n * 192));
     code = launch_bashF_batch(s.p, n, nullptr);

@@ -91,7 +91,7 @@ static err_t ctr_bulk(void *buf_, size_t count, void *ctr_state, bool allow_host
         if (count >= DUPLEX_MIN) {
             // all but the last (at most one) chunk through the duplex pipeline, whole blocks; what is left -- with the partial
             // block and the gamma the state keeps -- takes the plain path below, from the advanced counter
-            const size_t CH = (size_t)1 << g_duplex_log2_blocks;             // blocks per chunk (2^20 = 16 MiB)
+            const size_t CH = (size_t)1 << DUPLEX_LOG2_BLOCKS;             // blocks per chunk (2^20 = 16 MiB)
             const size_t pipe_blocks = (count - 1) / (16 * CH) * CH;
             err_t pc = ensure_device();
             if (pc != ERR_OK) return pc;

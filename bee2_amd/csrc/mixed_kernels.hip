@@ -682,12 +682,9 @@ err_t launch_belt_hash_stream(void *d_hs, const void *d_data, size_t nblocks, in
 // Long belt-hash messages (>= long_from bytes): a PAIR of lanes per message (belt_compress_pair): of the
 // three encryptions of a block the last two are independent, so the chain step is 2 E instead of 3.
 // Launched over all n messages (2 lanes each); pairs whose message is short leave at once.
-// (round 4) templated on the table and the workgroup for the A/B of profiles/r04_long_hash_ab.txt; a workgroup none of whose
-// pairs has a long message leaves before it fills the table (the caller sorts long messages to the front).
-// LANES = 2: a pair per message (belt_compress_pair); LANES = 4 (round 4): a quad -- each encryption walked by two lanes that
-// split the rounds' G-boxes (belt_encr_split: 4 levels of a round instead of 7 steps), the two second-stage encryptions by
-// the two pairs of the quad.  LANES = 8: every G-box shared by a quad, one S-box byte per lane (belt_encr_quad), two quads for the
-// second stage.
+// (round 4) templated on the table and the workgroup for the A/B of profiles/r04_long_hash_ab.txt, whose other forms are retired.
+// LANES = 2: a pair per message (belt_compress_pair); LANES = 8: every G-box shared by a quad, one S-box byte per lane
+// (belt_encr_quad), two quads for the second stage.
 template <class Tab, int LONG_WG, int LANES = 2>
 __global__ __launch_bounds__(LONG_WG)
 void belt_hash_long_kernel(const uint8_t *__restrict__ data, const uint64_t *__restrict__ off,
@@ -697,20 +694,16 @@ void belt_hash_long_kernel(const uint8_t *__restrict__ data, const uint64_t *__r
     // the 4 KiB table of the product sits in STATIC shared memory: its LDS address is then a compile-time constant and every
     // look-up address is "byte * 4 + immediate"; through the dynamic segment the base is a run-time value and each look-up pays
     // one more dependent add -- +16 % on a chain that is bound by exactly that latency (45.3 against 39.0 ms for a 256 KiB
-    // message, profiles/r04_long_hash_ab.txt).  The 64 KiB tables of the A/B forms need the dynamic segment (LDS address 0).
-    constexpr bool STATIC_TAB = Tab::kBytes <= 4096;
-    __shared__ __attribute__((aligned(16))) uint8_t smem_static[STATIC_TAB ? Tab::kBytes : 16];
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem_dyn[];
-    uint8_t *smem = STATIC_TAB ? smem_static : smem_dyn;
-    static_assert(LANES == 2 || LANES == 4 || LANES == 8, "lanes per message");
+    // message, profiles/r04_long_hash_ab.txt).
+    static_assert(Tab::kBytes <= 4096, "a table that fits static shared memory");
+    __shared__ __attribute__((aligned(16))) uint8_t smem[Tab::kBytes];
+    static_assert(LANES == 2 || LANES == 8, "lanes per message");
     const size_t slot = ((size_t)blockIdx.x * LONG_WG + threadIdx.x) / LANES;
     const uint32_t odd = (threadIdx.x & (unsigned)(LANES / 2)) ? ~0u : 0u;        // which second-stage encryption the lane (pair / quad) walks
-    const uint32_t rQ = (threadIdx.x & 1u) ? ~0u : 0u;                           // LANES == 4: the lane's column of the split rounds
     const BeltQuadLane QL(threadIdx.x & 3u);                                     // LANES == 8: the lane's S-box byte
-    (void)rQ; (void)QL;
+    (void)QL;
     const auto compress = [&](uint32_t (&s1)[4], uint32_t (&h)[8], const uint32_t (&X)[8], const Tab &T) {
         if constexpr (LANES == 8) belt_compress_oct(T.lds, QL, s1, h, X, odd);     // (a BeltTabSmall image)
-        else if constexpr (LANES == 4) belt_compress_quad(T, s1, h, X, rQ, odd);
         else belt_compress_pair(T, s1, h, X, odd);
     };
     size_t i = 0, len = 0;
@@ -719,18 +712,6 @@ void belt_hash_long_kernel(const uint8_t *__restrict__ data, const uint64_t *__r
         len = (size_t)(off[i + 1] - off[i]);
     }
     const bool mine = slot < n && len >= long_from;
-    if constexpr (!STATIC_TAB) {
-        // "is anything long here?" through the first word of the (dynamic) table area itself: a static __shared__ flag -- what
-        // __syncthreads_or allocates -- would push the table off LDS address 0, which its OR-composed addresses need
-        volatile uint32_t *flag = reinterpret_cast<volatile uint32_t *>(smem);
-        if (threadIdx.x == 0) *flag = 0;
-        __syncthreads();
-        if (mine) *flag = 1;
-        __syncthreads();
-        const uint32_t any = *flag;
-        __syncthreads();                                // everyone has read it before the fill overwrites it
-        if (!any) return;                               // nothing long in this workgroup: no table, no work
-    }
     Tab::fill(smem, threadIdx.x, LONG_WG);
     __syncthreads();
     const Tab T(smem);
@@ -840,14 +821,6 @@ void ragged_scatter_kernel(const uint64_t *__restrict__ off, size_t n, unsigned 
     if (i < n) order[base[b] + rank] = (uint32_t)i;
 }
 
-#ifdef BEE2HIP_EXPERIMENTS
-static int g_long_hash_form = 0;
-void set_long_hash_form(int v) { g_long_hash_form = v; }
-#endif
-static int g_ragged_fork = 1;               // long chains and short messages on two queues (0: one queue, the A/B of tools/ab/long_hash_ab.py)
-#ifdef BEE2HIP_EXPERIMENTS
-void set_ragged_fork(int v) { g_ragged_fork = v; }
-#endif
 constexpr uint64_t RAGGED_LONG = 4096;     // bytes; see bench.py --only ragged and DESIGN.md 4.7
 // secret (belt-hash only): the messages hold private keys (theta of bignSign2 with long additional input) -- every message, whatever
 // its length, goes through the kernel with the BANK-PRIVATE S-box copies (lane l only touches bank l & 31: the LDS cycles of a look-up
@@ -893,42 +866,13 @@ err_t launch_hash_ragged(size_t alg, const void *d_data, const void *d_off, cons
     // share the chip (round 4: the bench's ragged batch 32.4 -> 31.0 ms, profiles/r04_long_hash_ab.txt).  Small batches stay on one queue.
     hipStream_t st2 = st;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    const bool forked = n >= 1024 && g_ragged_fork && side_stream(&st2, &ev_fork, &ev_join) == ERR_OK;
+    const bool forked = n >= 1024 && side_stream(&st2, &ev_fork, &ev_join) == ERR_OK;
     if (forked) {
         B2H_TRY(hipEventRecord(ev_fork, st));
         B2H_TRY(hipStreamWaitEvent(st2, ev_fork, 0));
     } else
         st2 = st;
     if (alg == 0) {
-#ifdef BEE2HIP_EXPERIMENTS      // A/B (tune 16, tools/ab/long_hash_ab.py, profiles/r04_long_hash_ab.txt): the SDWA table in one-wavefront / four-wavefront workgroups
-        if (g_long_hash_form == 1) {      // the pair form (round 3's product) at every size
-            hipLaunchKernelGGL((belt_hash_long_kernel<BeltTabSmall, 64, 2>), dim3((unsigned)((n * 2 + 63) / 64)), dim3(64), 0, st, data, off, ord, n,
-                               dig, RAGGED_LONG);
-        } else if (g_long_hash_form == 7) {      // eight lanes per message: each G-box shared by a quad (one byte look-up per lane)
-            hipLaunchKernelGGL((belt_hash_long_kernel<BeltTabSmall, 64, 8>), dim3((unsigned)((n * 8 + 63) / 64)), dim3(64), 0, st, data, off, ord,
-                               n, dig, RAGGED_LONG);
-        } else if (g_long_hash_form == 5 || g_long_hash_form == 6) {      // a quad per message, rounds split over two lanes (4 KiB table / + SDWA addresses)
-            const dim3 gq((unsigned)((n * 4 + 63) / 64));
-            if (g_long_hash_form == 5)
-                hipLaunchKernelGGL((belt_hash_long_kernel<BeltTabSmall, 64, 4>), gq, dim3(64), 0, st, data, off, ord, n, dig, RAGGED_LONG);
-            else
-                hipLaunchKernelGGL((belt_hash_long_kernel<BeltTabSmallS, 64, 4>), gq, dim3(64), 0, st, data, off, ord, n, dig, RAGGED_LONG);
-        } else if (g_long_hash_form == 4) {
-            hipLaunchKernelGGL((belt_hash_long_kernel<BeltTabSmallS, 64>), dim3((unsigned)((n * 2 + 63) / 64)), dim3(64), 0, st, data, off, ord, n,
-                               dig, RAGGED_LONG);
-        } else if (g_long_hash_form == 2 || g_long_hash_form == 3) {
-            const int wg = g_long_hash_form == 2 ? 64 : 256;
-            const void *kern = wg == 64 ? reinterpret_cast<const void *>(belt_hash_long_kernel<BeltTabTwoP, 64>)
-                                        : reinterpret_cast<const void *>(belt_hash_long_kernel<BeltTabTwoP, 256>);
-            B2H_TRY(dyn_lds_once(kern, BeltTabTwo::kBytes));
-            if (wg == 64)
-                hipLaunchKernelGGL((belt_hash_long_kernel<BeltTabTwoP, 64>), dim3((unsigned)((n * 2 + 63) / 64)), dim3(64), BeltTabTwo::kBytes, st,
-                                   data, off, ord, n, dig, RAGGED_LONG);
-            else
-                hipLaunchKernelGGL((belt_hash_long_kernel<BeltTabTwoP, 256>), dim3((unsigned)((n * 2 + 255) / 256)), dim3(256), BeltTabTwo::kBytes,
-                                   st, data, off, ord, n, dig, RAGGED_LONG);
-        } else
-#endif
         // product (round 4): EIGHT lanes per long message -- every G-box shared by a quad, one S-box byte per lane, the two second-stage
         // encryptions on two quads (belt_compress_oct: 11.6 instead of 17 instructions per G-box and lane; a lone wavefront's chain
         // goes with the instructions it issues): 256 KiB in 26.6 ms against 32.5 ms for the pair form (round 3: 39).  Four times
@@ -998,25 +942,13 @@ err_t launch_belt_mac(void *d_states, const void *d_data, size_t stride, size_t 
     return ERR_OK;
 }
 
-// table of the MAC half: 0 = the product, 1 = BeltTabWide (four tables, 128 KiB: rounds 1-2), 2 = BeltTabTwoP (A/B: tune 13)
-static int g_fused_tab = 0;
-void set_fused_tab(int v) { g_fused_tab = v; }
-template <int RW, bool HASH, bool MAC, class Tab>
-static err_t launch_fused_tt(const void *d_msgs, size_t msg_len, size_t n, size_t l, const MacKey &key,
-                             void *d_digests, void *d_tags, hipStream_t st);
+// table of the MAC half: BeltTabWide (four tables, 128 KiB); the 64 KiB BeltTabTwoP measured +0.5 % only, bash-f's VALU
+// work bounds the kernel (profiles/r03_belt_sdwa_ab.txt)
 template <int RW, bool HASH, bool MAC>
 static err_t launch_fused_t(const void *d_msgs, size_t msg_len, size_t n, size_t l, const MacKey &key,
                             void *d_digests, void *d_tags, hipStream_t st)
 {
-#ifdef BEE2HIP_EXPERIMENTS      // A/B only (tools/ab/fused_tab_ab.py): +0.5 %, bash-f's VALU work bounds the kernel
-    if (MAC && g_fused_tab == 2) return launch_fused_tt<RW, HASH, MAC, BeltTabTwoP>(d_msgs, msg_len, n, l, key, d_digests, d_tags, st);
-#endif
-    return launch_fused_tt<RW, HASH, MAC, BeltTabWide>(d_msgs, msg_len, n, l, key, d_digests, d_tags, st);
-}
-template <int RW, bool HASH, bool MAC, class Tab>
-static err_t launch_fused_tt(const void *d_msgs, size_t msg_len, size_t n, size_t l, const MacKey &key,
-                             void *d_digests, void *d_tags, hipStream_t st)
-{
+    using Tab = BeltTabWide;
     auto kern = hash_mac_fused_kernel<RW, HASH, MAC, Tab>;
     const size_t lds = MAC ? (size_t)Tab::kBytes : 0;
     if (MAC) B2H_TRY(dyn_lds_once(reinterpret_cast<const void *>(kern), lds));

@@ -401,10 +401,9 @@ static err_t with_host(int kind, size_t bytes, const char *what, G gpu, H host)
 // the copy on the same stream; a helper thread downloads chunk c - 1 on a second stream as soon as its kernel is through.
 // launch(dev_chunk, first_unit, units, stream) queues the kernel(s) for `units` units starting at unit `first_unit`.
 constexpr size_t DUPLEX_MIN = (size_t)48 << 20;          // below this the two copies cost < 2 ms: not worth a thread
-static int g_duplex_log2_states = 16, g_duplex_log2_blocks = 20;   // chunk sizes (bee2hip_internal_tune 6 / 7: sweep)
+constexpr int DUPLEX_LOG2_STATES = 16, DUPLEX_LOG2_BLOCKS = 20;   // chunk sizes: bashF states / belt blocks (profiles/r03_pcie_duplex.txt)
 constexpr size_t VERIFY_PIPE_MIN = (size_t)1 << 19, VERIFY_PIPE_CHUNK = (size_t)1 << 18;   // host-pointer verification batches
 static int g_verify_pipe = 1;                                      // (tune 11: A/B)
-static int g_duplex_ramp = 0;                                      // quarter / half chunks at both ends (tune 9): measured -2 %, off
 #ifdef BEE2HIP_EXPERIMENTS
 static std::atomic<int> g_duplex_fail_chunk{0}, g_duplex_fail_times{0};   // tests (tune 14 / 15): the next `times` pipelines fail at chunk `chunk`
 #endif
@@ -482,22 +481,13 @@ static err_t duplex_inplace(octet *host, octet *dev, size_t unit_bytes, size_t u
     if (done_units) *done_units = 0;
     err_t code = t_duplex.get();
     if (code != ERR_OK) return code;
-    // chunk boundaries: full chunks, with a quarter and a half chunk at either end when there are enough of them -- the first
-    // upload and the last download are the only transfers with nothing in the other direction beside them (knob 9)
+    // chunk boundaries: full chunks, the last one takes the rest (quarter and half chunks at either end measured -2 %:
+    // profiles/r03_pcie_duplex.txt)
     std::vector<size_t> cut;
     {
-        const size_t q = chunk_units / 4, h = chunk_units / 2;
-        const bool ramp = g_duplex_ramp && q && units >= 6 * chunk_units;
         size_t pos = 0;
         cut.push_back(0);
-        if (ramp) { cut.push_back(pos += q); cut.push_back(pos += h); }
-        const size_t tail = ramp ? q + h : 0;
-        while (units - pos > chunk_units + tail) cut.push_back(pos += chunk_units);
-        if (ramp) {
-            const size_t rest = units - pos - tail;       // <= chunk_units, > 0
-            cut.push_back(pos += rest);
-            cut.push_back(pos += h);
-        }
+        while (units - pos > chunk_units) cut.push_back(pos += chunk_units);
         cut.push_back(units);
     }
     const size_t nch = cut.size() - 1;

@@ -8,8 +8,8 @@ import subprocess
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB_PATH = os.path.join(PKG, "lib", "libbee2hip.so")
-# the same sources with -DBEE2HIP_EXPERIMENTS: rejected kernel variants kept for the A/B record and the bee2hip_internal_* /
-# bee2hip_debug_fe* / bee2hip_time_kernel hooks of include/bee2hip_internal.h.  tests/ and tools/ load it where they need a
+# the same sources with -DBEE2HIP_EXPERIMENTS: the product kernels plus the bee2hip_internal_* / bee2hip_debug_fe* /
+# bee2hip_time_kernel hooks of include/bee2hip_internal.h.  tests/ and tools/ load it where they need a
 # hook; nothing a bee2 caller links against is in it only.
 EXP_LIB_PATH = os.path.join(PKG, "lib", "libbee2hip_exp.so")
 
@@ -696,7 +696,7 @@ _exp_engine = None
 
 
 def load_experiments(path=EXP_LIB_PATH):
-    """Load libbee2hip_exp.so (the -DBEE2HIP_EXPERIMENTS build: test hooks + the A/B variants).  A second, independent copy of
+    """Load libbee2hip_exp.so (the -DBEE2HIP_EXPERIMENTS build: the product kernels + test hooks).  A second, independent copy of
     the library in the process: its own staging buffers, scratch pools and policy switches."""
     global _exp_engine
     if _exp_engine is None:

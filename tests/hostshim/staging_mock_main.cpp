@@ -65,9 +65,8 @@ static err_t launch_tf(octet *d, size_t unit_bytes, size_t first, size_t cnt, hi
 }
 static void fill(std::vector<octet> &v, unsigned seed) { for (size_t i = 0; i < v.size(); ++i) v[i] = (octet)((i * 2654435761u + seed) >> 13); }
 
-static void duplex_ok(size_t unit_bytes, size_t units, size_t chunk, int ramp)
+static void duplex_ok(size_t unit_bytes, size_t units, size_t chunk)
 {
-    if (ramp >= 0) g_duplex_ramp = ramp;                  // (-1: leave the knob alone -- the concurrent callers below must not write it)
     std::vector<octet> host(unit_bytes * units), want;
     fill(host, (unsigned)(units + chunk));
     want = host;
@@ -84,7 +83,6 @@ static void duplex_ok(size_t unit_bytes, size_t units, size_t chunk, int ramp)
 // mode 1: the launcher reports an error at chunk `bad`; 2: it throws std::bad_alloc there; 3: it throws something else
 static void duplex_fails(size_t units, size_t chunk, size_t bad, int mode)
 {
-    g_duplex_ramp = 0;
     const size_t ub = 16;
     std::vector<octet> host(ub * units), orig;
     fill(host, 99);
@@ -197,12 +195,10 @@ static void worker_pool()
 int main()
 {
     CHECK(ensure_device() == ERR_OK);
-    for (int ramp = 0; ramp < 2; ++ramp) {
-        duplex_ok(16, 1, 4, ramp);
-        duplex_ok(16, 1000, 64, ramp);
-        duplex_ok(192, 777, 100, ramp);
-        duplex_ok(16, 64 * 40, 64, ramp);
-    }
+    duplex_ok(16, 1, 4);
+    duplex_ok(16, 1000, 64);
+    duplex_ok(192, 777, 100);
+    duplex_ok(16, 64 * 40, 64);
     for (int mode = 1; mode <= 3; ++mode) {
         duplex_fails(64 * 10, 64, 0, mode);
         duplex_fails(64 * 10, 64, 4, mode);
@@ -210,7 +206,7 @@ int main()
     }
     {   // several host threads, each with its own pipeline (streams are per thread)
         std::vector<std::thread> th;
-        for (int t = 0; t < 4; ++t) th.emplace_back([t] { duplex_ok(16, 3000 + 100 * t, 128, -1); });
+        for (int t = 0; t < 4; ++t) th.emplace_back([t] { duplex_ok(16, 3000 + 100 * t, 128); });
         for (auto &t : th) t.join();
     }
     pool_and_fallback();

@@ -54,13 +54,31 @@ def test_product_library_ships_no_hooks_and_no_experiment_kernels(lib_path):
     import subprocess
     names = subprocess.check_output([os.path.join(ROOT, "tools", "list_kernels.sh"), lib_path], text=True).splitlines()
     kernels = sorted({n.split("(")[0] for n in names if n.strip()})
-    assert kernels and len(kernels) <= 148, len(kernels)          # 124 + the one-signer / few-signers family (key table, main in three forms x 3 curves, the fallback's key replication)
+    assert kernels and len(kernels) <= 146, len(kernels)          # 124 + the one-signer / few-signers family (key table, main in three forms x 3 curves, the fallback's key replication)
     for bad in ("debug", "clock_probe", "bashF_batch_kernel", "bashF_walk_kernel", "BeltTabHyb", "BeltTabTwoS", "BeltTabTwoL",
-                "BeltTabTwoQ"):
+                "BeltTabTwoQ", "BeltTabTwoPT<true>", "BeltTabSmallS", "bign_gtable6_kernel<8, 7>"):
         assert not [k for k in kernels if bad in k], bad
     assert len([k for k in kernels if "bashF_tile_kernel" in k]) == 1
     assert len([k for k in kernels if "beltCTR_blocks_kernel" in k]) == 2          # with / without the hoisted round-1 G-box
     assert len([k for k in kernels if "bign_mulbase_ct_kernel" in k]) == 3         # one per curve
+
+
+def _kernel_set(path):
+    import subprocess
+    names = subprocess.check_output([os.path.join(ROOT, "tools", "list_kernels.sh"), path], text=True).splitlines()
+    return {n for n in names if n.strip()}
+
+
+def test_experiments_library_holds_the_product_kernels_and_the_hook_kernels(lib_path):
+    """libbee2hip_exp.so is the product plus test hooks: its kernels are exactly the product's and the kernels of the
+    hooks of include/bee2hip_internal.h (bee2hip_debug_fe{,L}: bign_debug_fe_kernel per curve; bee2hip_internal_clock_probe)"""
+    if not os.path.exists(E.EXP_LIB_PATH):
+        pytest.skip("libbee2hip_exp.so not built")
+    prod, exp = _kernel_set(lib_path), _kernel_set(E.EXP_LIB_PATH)
+    hooks = {f"bee2hip::bign_debug_fe_kernel<{n}>(int, unsigned int const*, unsigned int const*, unsigned int*, unsigned long)"
+             for n in (8, 12, 16)} | {"clock_probe_kernel(unsigned long long*, unsigned long long)"}
+    assert not (prod & hooks)
+    assert exp == prod | hooks, (sorted(exp - prod - hooks), sorted((prod | hooks) - exp))
 
 
 def test_experiments_library_exports_the_hooks():

@@ -92,6 +92,10 @@ def test_golden_cases_dropin(golden, l, mulbase):
             assert rng.pos[0] == 0                    # a bad private key must not consume the generator
 
 
+# forms of k G that earlier rounds forced through the hook and that have been retired (bee2hip_internal_tune(10, v) refuses them)
+RETIRED_MULBASE = (7, 72, 101, 102)
+
+
 @pytest.fixture(params=["auto", "gpu", 1, 7, 72, 8, 101, 102, 4, 16, 64],
                 ids=lambda v: {"auto": "product_library_auto_single_calls_on_the_host", "gpu": "product_library_forced_gpu",
                                7: "1_lane_7bit_windows_looked_up_in_LDS", 72: "1_lane_7bit_LDS_other_coordinates", 8: "1_lane_8bit_windows_LDS_16_copies", 101: "1_lane_4bit_windows",
@@ -101,10 +105,12 @@ def mulbase(request):
     on the calling core in constant-time host arithmetic (bee2_amd/csrc/host_bign_ct.hpp), batches on the GPU with the kernel
     picked by batch size; "gpu": the product library under BEE2HIP_FORCE=gpu semantics (every secret in the kernels).  The
     numbers: one GPU form FORCED at every size through the hook of the experiments build (libbee2hip_exp.so, also forced to the
-    GPU): one lane per scalar (bign_mulbase_ct_kernel: signed 6-bit windows and Jacobian mixed additions; 7 = signed 7-bit windows with the
-    entry looked up in LDS, bign_mulbase_lds_kernel: the throughput form of the 256-bit curve from 2^18 scalars on -- the other curves fall back to 1; 102 =
-    the same windows with complete additions, 101 = the round-2 form on unsigned 4-bit windows) or 4 / 16 / 64 lanes per scalar
-    (bign_mulbase_coop_kernel).  Yields the engine to use; defaults restored."""
+    GPU): one lane per scalar (bign_mulbase_ct_kernel: signed 6-bit windows and Jacobian mixed additions; 8 = signed 8-bit
+    windows with the entry looked up in LDS, bign_mulbase_lds_kernel: the throughput form of the 256-bit curve -- the other
+    curves fall back to the choice by size) or 4 / 16 / 64 lanes per scalar (bign_mulbase_coop_kernel).  7 / 72 (7-bit LDS
+    windows), 101 (4-bit windows) and 102 (complete additions) name forms that are retired: the hook must refuse them with
+    ERR_BAD_INPUT and leave the product's choice by batch size in place, which then has to pass the same checks.  Yields the
+    engine to use; defaults restored."""
     if request.param in ("auto", "gpu"):
         eng = engine()
         was = eng.lib.bee2hip_path_policy(1 if request.param == "gpu" else 0)
@@ -118,7 +124,11 @@ def mulbase(request):
         return
     eng = exp_engine()
     was = eng.lib.bee2hip_path_policy(1)
-    eng.lib.bee2hip_internal_tune(10, request.param)
+    if request.param in RETIRED_MULBASE:
+        assert eng.lib.bee2hip_internal_tune(10, 0) == 0
+        assert eng.lib.bee2hip_internal_tune(10, request.param) == E.ERR_BAD_INPUT
+    else:
+        assert eng.lib.bee2hip_internal_tune(10, request.param) == 0
     yield eng
     eng.lib.bee2hip_internal_tune(10, 0)
     eng.lib.bee2hip_path_policy(was)

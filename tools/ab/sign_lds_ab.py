@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B of the one-lane k G forms of the signing side on the 256-bit curve (experiments build, bee2hip_internal_tune 10):
-1 = signed 6-bit windows, masked scan of the row (round 3's product); 7 = signed 7-bit windows looked up in LDS, product
-coordinates; 72 = the same with the other coordinate form.  Device-resident batches, hipEvents, outputs asserted identical.
+1 = signed 6-bit windows, masked scan of the row (round 3's product); 8 = signed 8-bit windows looked up in LDS; 0 = the
+product dispatch by size.  Device-resident batches, hipEvents, outputs asserted identical.
 usage: python tools/ab/sign_lds_ab.py"""
 import os
 import sys
@@ -30,8 +30,8 @@ def ms(fn, reps=10):
     return e0.elapsed_time(e1) / reps
 
 
-FORMS = tuple(int(x) for x in sys.argv[1].split(",")) if len(sys.argv) > 1 else (1, 0, 7, 8)      # (round 6: 81 = the 8-bit LDS form on 32-bit limbs, 8 / 0 = on 29-bit limbs)
-print("ms per batch (pubkey calc | sign2) and M/s; forms: 1 = 6-bit scan, 0 = product dispatch by size (4 lanes up to 2^15, 8-bit LDS from 3*2^14: 512- / 1024-lane workgroups), 7 = 7-bit LDS, 8 = 8-bit LDS forced")
+FORMS = tuple(int(x) for x in sys.argv[1].split(",")) if len(sys.argv) > 1 else (1, 0, 8)
+print("ms per batch (pubkey calc | sign2) and M/s; forms: 1 = 6-bit scan, 0 = product dispatch by size (4 lanes up to 2^15, 8-bit LDS from 3*2^14: 512- / 1024-lane workgroups), 8 = 8-bit LDS forced")
 for e in (15, 16, 17, 18, 19):
     n = 1 << e
     g = torch.Generator(device="cuda"); g.manual_seed(5)
