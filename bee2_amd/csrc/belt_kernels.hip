@@ -639,6 +639,14 @@ int cur_dev()
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     return dev;
 }
+bool stream_is_capturing(hipStream_t st)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (st && hipStreamIsCapturing(st, &cs) == hipSuccess) return cs == hipStreamCaptureStatusActive;
+    (void)hipGetLastError();
+    return false;
+}
+
 int num_cus()
 {
     const int dev = cur_dev();

@@ -1837,6 +1837,7 @@ struct KeyTab {
 // all taken stays on its 8-bit table
 constexpr int KEYTAB16_MAX = 96;
 static std::atomic<int> g_keytab16_live{0};
+unsigned long long bign_onekey_tab16_live() { return (unsigned long long)g_keytab16_live.load(); }
 KeyTab::~KeyTab() { if (tab16) { (void)hipFree(tab16); g_keytab16_live.fetch_sub(1); } }
 static size_t KEYTAB_SLOTS = 1024;                   // (0.3 - 1 GiB of 8-bit tables when full; tests: tune 21)
 void set_onekey_slots(int v) { KEYTAB_SLOTS = v < 1 ? 1 : (size_t)v; }
@@ -1887,6 +1888,12 @@ static err_t bign_key_tables(std::vector<std::shared_ptr<KeyTab>> &out, const ui
     const int lg = g_keytab16_log2 >= 0 ? g_keytab16_log2 : N == 8 ? 19 : 20;
     const uint64_t after = lg >= 63 ? ~(uint64_t)0 : (uint64_t)1 << lg;
     out.assign(nkeys, nullptr);
+    // On a stream that is being captured only queued work is legal.  The 16-bit table of a busy key costs an allocation, a launch
+    // and a synchronisation, so a captured call never promotes a key -- it runs on the tables the key has -- and does not count
+    // towards the promotion either (a capture queues nothing: the replays verify, and the library does not see them).  The next
+    // eager call under the key promotes it as usual.
+    const bool capturing = stream_is_capturing(st);
+    if (capturing) want16 = false;
     const auto id_of = [&](const uint8_t *key) {
         std::string id(2 + 2 * NO, '\0');
         id[0] = (char)dev; id[1] = (char)N;
@@ -1906,7 +1913,7 @@ static err_t bign_key_tables(std::vector<std::shared_ptr<KeyTab>> &out, const ui
         if (it != g_keytabs.end()) {
             KeyTab *t = it->second.get();
             t->stamp = ++g_keytab_clock;
-            t->used += n;
+            if (!capturing) t->used += n;
             if (want16 && !t->tab16 && t->used >= after) { const err_t c = bign_key_table16_locked<N>(*t, st); if (c != ERR_OK) return c; }
             out[k] = it->second;
             continue;
@@ -1920,11 +1927,8 @@ static err_t bign_key_tables(std::vector<std::shared_ptr<KeyTab>> &out, const ui
         {
             // a key this process has not met needs an allocation, an upload and a synchronisation: none of that is legal on a stream
             // that is being captured (and would kill the capture).  Say so instead: verify once under the key outside the capture.
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (st && hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) {
+            if (capturing)
                 return hip_fail(hipErrorStreamCaptureUnsupported, "key-table miss under stream capture: verify once under each key before capturing");
-            }
-            (void)hipGetLastError();
         }
         // on the curve?  then the 2N + 1 starting points -- host threads when there are many keys
         std::vector<std::vector<uint8_t>> base(miss.size());
@@ -2047,6 +2051,11 @@ static err_t launch_bign_verify_onekey_t(const uint8_t *oid_der, size_t oid_len,
 {
     constexpr size_t NO = 4 * N;
     const bool keyed = d_key_index != nullptr;
+    const bool capturing = stream_is_capturing(st);
+    // the keyed form uploads the keys and the tables' addresses from pageable memory and waits for the copy, on every call
+    if (keyed && capturing)
+        return hip_fail(hipErrorStreamCaptureUnsupported, "keyed verification under stream capture: this entry uploads and synchronises per call; "
+                                                          "capture the one-signer entry per key instead");
     uint4 *gtab = nullptr;
     err_t code;
     {
@@ -2062,13 +2071,12 @@ static err_t launch_bign_verify_onekey_t(const uint8_t *oid_der, size_t oid_len,
         // A stream CAPTURE bakes the tables' addresses into the graph, and nothing tells the library when that graph dies: the tables
         // a capture refers to are pinned for the life of the process (a reference that is never dropped), so neither the LRU nor a
         // later call's eviction can free memory a replay will read.  Bounded by the distinct keys ever captured.
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (st && hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) {
+        if (capturing) {
             std::lock_guard<std::mutex> lk(g_keytab_mu);
             static std::vector<std::shared_ptr<KeyTab>> &pinned = *new std::vector<std::shared_ptr<KeyTab>>;
             for (const auto &t : kts)
                 if (t && std::find(pinned.begin(), pinned.end(), t) == pinned.end()) pinned.push_back(t);
-        } else (void)hipGetLastError();
+        }
     }
     const uint4 *tab16 = nullptr;
     const uint8_t *d_keys = nullptr;

@@ -14,6 +14,7 @@
 //   capi_mixed.hip  bash + belt-MAC per message, ragged hash batches, path policy
 //   capi_exp.hip    experiment hooks (libbee2hip_exp.so only)
 #include "staging.hpp"
+static const bool g_capture_query_set = (bee2hip::g_stream_capturing = bee2hip::stream_is_capturing, true);
 #include "capi_base.hip"
 #include "capi_bash.hip"
 #include "capi_belt.hip"

@@ -269,6 +269,8 @@ extern "C" err_t bee2hip_beltModes_blocks_dev(int mode, const void *d_src, void 
 try {
     if (misaligned(d_src, 16) || misaligned(d_dst, 16)) return ERR_BAD_INPUT;
     if ((nblocks && (!d_src || !d_dst)) || !key || (mode == 2 && !iv)) return ERR_BAD_INPUT;
+    // in place or disjoint (CBC decryption, which reads block i - 1 next to block i: disjoint, launch_belt_modes refuses in place)
+    if (nblocks && partly_overlap(d_src, d_dst, nblocks * 16)) return ERR_BAD_INPUT;
     err_t code = ensure_device();
     if (code != ERR_OK) return code;
     return launch_belt_modes(mode, d_src, d_dst, nblocks, key, iv, as_stream(stream));
@@ -690,6 +692,7 @@ extern "C" err_t bee2hip_beltCHE_blocks_dev(const void *d_src, void *d_dst, size
 try {
     if (misaligned(d_src, 16) || misaligned(d_dst, 16)) return ERR_BAD_INPUT;
     if ((nblocks && (!d_src || !d_dst)) || !key || !s) return ERR_BAD_INPUT;
+    if (nblocks && partly_overlap(d_src, d_dst, nblocks * 16)) return ERR_BAD_INPUT;      // in place or disjoint
     if (first_block + nblocks < first_block || first_block + nblocks == ~(uint64_t)0) return ERR_BAD_INPUT;
     err_t code = ensure_device();
     if (code != ERR_OK) return code;
@@ -800,6 +803,7 @@ extern "C" err_t bee2hip_beltBDE_blocks_dev(int decr, const void *d_src, void *d
 try {
     if (misaligned(d_src, 16) || misaligned(d_dst, 16)) return ERR_BAD_INPUT;
     if ((nblocks && (!d_src || !d_dst)) || !key || !s || (decr != 0 && decr != 1)) return ERR_BAD_INPUT;
+    if (nblocks && partly_overlap(d_src, d_dst, nblocks * 16)) return ERR_BAD_INPUT;      // in place or disjoint
     if (first_block + nblocks < first_block || first_block + nblocks == ~(uint64_t)0) return ERR_BAD_INPUT;
     err_t code = ensure_device();
     if (code != ERR_OK) return code;

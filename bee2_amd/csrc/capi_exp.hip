@@ -29,6 +29,7 @@ try {
 extern "C" unsigned long long bee2hip_internal_stat(int which)
 {
     if (which == 4) return bee2hip::g_new_calls.load();               // operator new calls of the library so far (tune 24's clock)
+    if (which == 5) return bee2hip::bign_onekey_tab16_live();         // 16-bit key tables alive now (busy keys of one-signer / few-signers verification)
     if (which == 3) return bee2hip::bign_onekey_table_builds();       // key tables built so far (one-signer / few-signers verification)
     return which == 0 ? bee2hip::g_n_host.load() : which == 1 ? bee2hip::g_n_gpu.load() : bee2hip::g_n_fallback.load();
 }

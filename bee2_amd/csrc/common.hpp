@@ -33,6 +33,8 @@ const uint8_t *host_beltH();                              // the belt S-box, gen
 // per-device launch facts and the once-per-(device, kernel) dynamic-LDS grant (belt_kernels.hip)
 int cur_dev();
 int num_cus();
+// true while `st` is being captured into a graph (never the NULL stream): only queued work is legal on it then
+bool stream_is_capturing(hipStream_t st);
 hipError_t dyn_lds_once(const void *kern, size_t bytes);
 err_t upload_beltH(const uint8_t *H);            // the S-box copy of bee2hip_tu_belt.hip
 err_t upload_beltH_bign(const uint8_t *H);       // ... of bee2hip_tu_bign.hip
@@ -87,6 +89,7 @@ err_t launch_bign_verify_keyed(size_t l, const uint8_t *oid_der, size_t oid_len,
                                const uint8_t *pubkeys, size_t nkeys, const void *d_key_index, size_t n, void *d_codes, hipStream_t st);
 err_t launch_replicate_key(const void *d_key, size_t key_bytes, size_t n, void *d_out, hipStream_t st);
 unsigned long long bign_onekey_table_builds();
+unsigned long long bign_onekey_tab16_live();
 // non-standard parameter sets (bign_generic_kernels.hip): params already through bignParamsCheck's tests
 err_t launch_bign_verify_generic(const bign_params *params, const uint8_t *oid_der, size_t oid_len, const void *d_hashes,
                                  const void *d_sigs, const void *d_pubkeys, size_t n, void *d_codes, hipStream_t st);

@@ -156,6 +156,11 @@ struct ThreadReaper {
 };
 static thread_local ThreadReaper t_reaper;
 
+// "is this stream being captured into a graph?" -- the library points it at stream_is_capturing (capi.hip).  A pointer, not a
+// call of the runtime: this file is also compiled on its own against a stand-in runtime that has streams and events but no
+// graphs (tests/hostshim), where it stays null.
+static bool (*g_stream_capturing)(hipStream_t) = nullptr;
+
 err_t scratch_for_stream(hipStream_t st, int slot, size_t bytes, void **out)
 {
     int dev = 0;
@@ -174,6 +179,11 @@ err_t scratch_for_stream(hipStream_t st, int slot, size_t bytes, void **out)
         e = &g_pool.back();
     }
     if (e->bytes < bytes) {
+        // growing needs an allocation (and a synchronise when a block is replaced): neither is legal on a stream that is being
+        // captured, and either would invalidate the capture.  Refuse before anything touches the stream.
+        if (g_stream_capturing && g_stream_capturing(st))
+            return hip_fail(hipErrorStreamCaptureUnsupported,
+                            "scratch growth under stream capture: call once eagerly with the largest size before capturing");
         if (e->p) {
             B2H_TRY(hipStreamSynchronize(st));            // earlier batches may still use the old block
             (void)hipFree(e->p);
@@ -584,3 +594,11 @@ using namespace bee2hip;
 // The kernels read blocks / states / field elements as 16-byte vectors: a misaligned device pointer
 // would be a GPU memory fault, so the _dev entry points refuse it with ERR_BAD_INPUT instead.
 static inline bool misaligned(const void *p, size_t a) { return p && ((uintptr_t)p & (a - 1)) != 0; }
+// The block-mode kernels take source and destination as __restrict__ pointers: the two ranges are either the same
+// range (in place, where the mode allows it) or disjoint.  True for two ranges of `bytes` bytes that share bytes
+// without starting at the same address.
+static inline bool partly_overlap(const void *a, const void *b, size_t bytes)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x != y && (x < y ? y - x : x - y) < bytes;
+}

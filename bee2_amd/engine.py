@@ -296,6 +296,14 @@ class Engine:
             self._ptr(hashes), self._ptr(sigs), self._ptr(pubkeys), _sz(n), self._ptr(codes),
             self._stream()), "bign128Verify_batch_dev")
 
+    def bignVerify_batch_dev(self, oid_der, hashes, sigs, pubkeys, codes):
+        """the 256-bit curve (l = 128) with the caller's OID"""
+        n = hashes.numel() // 32
+        assert sigs.numel() == 48 * n and pubkeys.numel() == 64 * n and codes.numel() >= n
+        self._check(self.lib.bee2hip_bignVerify_batch_dev(
+            bytes(oid_der), _sz(len(oid_der)), self._ptr(hashes), self._ptr(sigs), self._ptr(pubkeys), _sz(n), self._ptr(codes),
+            self._stream()), "bignVerify_batch_dev")
+
     def bignVerifyL_batch_dev(self, l, oid_der, hashes, sigs, pubkeys, codes):
         n = hashes.numel() // (l // 4)
         assert sigs.numel() == (3 * l // 8) * n and pubkeys.numel() == (l // 2) * n and codes.numel() >= n
@@ -338,9 +346,12 @@ class Engine:
     def hash_ragged_dev(self, alg, data, offsets, digests, n, order=None):
         """alg 0 = belt-hash, 128/192/256 = bash256/384/512; data (u8), offsets (int64, n+1),
         digests (u8) and the optional launch order (int32 permutation, longest message first) are
-        device tensors"""
-        o = self._ptr(order) if order is not None else None
-        self._check(self.lib.bee2hip_hash_ragged_ordered_dev(_sz(alg), self._ptr(data), self._ptr(offsets), o,
+        device tensors; without an order the library buckets the messages by length itself (bee2hip_hash_ragged_dev)"""
+        if order is None:
+            self._check(self.lib.bee2hip_hash_ragged_dev(_sz(alg), self._ptr(data), self._ptr(offsets), _sz(n), self._ptr(digests),
+                                                         self._stream()), "hash_ragged_dev")
+            return
+        self._check(self.lib.bee2hip_hash_ragged_ordered_dev(_sz(alg), self._ptr(data), self._ptr(offsets), self._ptr(order),
                                                              _sz(n), self._ptr(digests), self._stream()),
                     "hash_ragged_ordered_dev")
 

@@ -377,14 +377,16 @@ err_t bee2hip_beltCTR_blocks_dev(void *d_buf, size_t nblocks, const u32 key[8],
 /* ECB-style E_K over n blocks in place (used for ctr0 = E_K(iv), r = E_K(0)) */
 err_t bee2hip_beltBlockEncr_dev(void *d_blocks, size_t nblocks, const u32 key[8], void *stream);
 /* 8f-1: full blocks, device resident.  mode 0 = ECB encrypt, 1 = ECB decrypt (d_src may equal
-   d_dst), 2 = CBC decrypt with chaining value iv[4] (u32 words; d_src != d_dst) */
+   d_dst), 2 = CBC decrypt with chaining value iv[4] (u32 words; d_src != d_dst).  Source and
+   destination ranges that overlap in any other way are refused with ERR_BAD_INPUT. */
 err_t bee2hip_beltModes_blocks_dev(int mode, const void *d_src, void *d_dst, size_t nblocks,
                                    const u32 key[8], const u32 iv[4], void *stream);
 /* n independent messages of nblk full blocks each, CBC-encrypted in place, one lane per
    message; d_ivs[n][16] holds each message's iv on entry and its last ciphertext block on exit */
 err_t bee2hip_beltCBCEncr_batch_dev(void *d_msgs, size_t nblk, size_t n, const u32 key[8],
                                     void *d_ivs, void *stream);
-/* belt-bde on nblocks whole blocks, device resident, d_src may equal d_dst.  s[4] = E_K(iv) as
+/* belt-bde on nblocks whole blocks, device resident, d_src may equal d_dst (ranges that overlap in any
+   other way are refused with ERR_BAD_INPUT).  s[4] = E_K(iv) as
    u32 words (what beltBDEStart leaves in the state); the blocks are the ones first_block ..
    first_block + nblocks - 1 of the stream, i.e. block j uses the tweak s * x^(j+1) -- a stream can
    be cut into pieces (or sharded across GPUs) at any block boundary.  decr = 0 / 1.
@@ -399,7 +401,8 @@ err_t bee2hip_beltDWP_absorb_dev(const void *d_data, size_t nbytes, const u32 r[
    resident, in place; d_ivs = nsectors x 16 bytes, one iv per sector.  decr = 0 / 1. */
 err_t bee2hip_beltSDE_sectors_dev(int decr, void *d_sectors, size_t sector_bytes, size_t nsectors,
                                   const u32 key[8], const void *d_ivs, void *stream);
-/* belt-che keystream on nblocks whole blocks, device resident, d_src may equal d_dst: block j of the
+/* belt-che keystream on nblocks whole blocks, device resident, d_src may equal d_dst (ranges that overlap
+   in any other way are refused with ERR_BAD_INPUT): block j of the
    stream (first_block <= j < first_block + nblocks) is XORed with E_K(S_{j+1}), S_0 = s[4] = E_K(iv) as
    u32 words, S_i = S_{i-1}*x ^ 1.  d_s_out (may be NULL) receives S_{first_block + nblocks}, 16 bytes. */
 err_t bee2hip_beltCHE_blocks_dev(const void *d_src, void *d_dst, size_t nblocks, const u32 key[8],
@@ -425,7 +428,8 @@ err_t bee2hip_bignVerifyL_batch_dev(size_t l, const octet oid_der[], size_t oid_
    doublings left.  pubkey is HOST memory in both forms (l/2 octets).  A key that is not a point of the curve, and a
    non-standard parameter set, take the general path with the key repeated -- same codes, general speed.
    The _dev form synchronises `stream` the first time it meets a key (table construction); later calls with that key
-   only queue kernels (hipGraph capture: prime the key with one call before capturing). */
+   only queue kernels (hipGraph capture: prime the key with one call before capturing; a key the cache does not hold is
+   refused on a capturing stream, and a captured call neither builds nor counts towards the key's 16-bit table). */
 err_t bee2hip_bignVerify_onekey_batch(const bign_params *params, const octet oid_der[], size_t oid_len,
                                       const octet *hashes, const octet *sigs, const octet pubkey[],
                                       size_t n, err_t *codes);
@@ -436,7 +440,8 @@ err_t bee2hip_bignVerifyL_onekey_batch_dev(size_t l, const octet oid_der[], size
    signature i is (n x u32; device memory in the _dev form).  codes[i] = bignVerify(params, oid, hash_i, sig_i, pubkeys[key_index[i]]);
    an index out of range gives ERR_BAD_INPUT for that signature.  Every key gets its cached 8-bit comb table (the last 1024 keys
    per process) and, once it has been busy enough, the 16-bit one; a key that is not a point of the curve costs ITS signatures the
-   complete slow kernel, nothing else.  This form uploads keys and table addresses per call (a copy and a synchronisation). */
+   complete slow kernel, nothing else.  This form uploads keys and table addresses per call (a copy and a synchronisation):
+   the _dev form is refused on a capturing stream. */
 err_t bee2hip_bignVerify_keyed_batch(const bign_params *params, const octet oid_der[], size_t oid_len,
                                      const octet *hashes, const octet *sigs, const octet *pubkeys, size_t nkeys,
                                      const u32 *key_index, size_t n, err_t *codes);

@@ -47,7 +47,8 @@ err_t bee2hip_internal_tune(int key, int value);
    the signatures after which a key gets its 16-bit table, keys the table cache keeps, four lanes per signature; key 24 =
    the value-th operator new of the library from now on throws std::bad_alloc) */
 /* drop-in helper calls so far: which = 0 taken on the host path, 1 on the GPU, 2 finished on the host after the GPU path
-   failed twice */
+   failed twice; 3 = key tables built so far and 5 = 16-bit key tables alive now (one-signer / few-signers verification);
+   4 = operator new calls of the library so far */
 unsigned long long bee2hip_internal_stat(int which);
 
 #if defined(__GNUC__)

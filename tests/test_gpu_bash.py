@@ -68,7 +68,7 @@ def test_bash_hash_A3_dropin(golden):
 def test_bash_hash_levels_and_splits_vs_oracle(orc):
     eng = engine()
     msg = orc.fill(1000, 42)
-    for l in (16, 32, 64, 128, 144, 192, 256):
+    for l in range(16, 257, 16):                  # every level bashHash accepts: rates of 23 .. 8 words
         for n in (0, 1, 63, 64, 65, 184, 191, 192, 193, 500, 1000):
             assert eng.bashHash(l, msg[:n]) == orc.bashHash(l, msg[:n])
     d, ok = eng.bashHash_steps(256, msg, [1, 62, 1, 64, 200, 672])
@@ -81,7 +81,7 @@ def test_bash_hash_large_chunks_all_levels(orc):
     a large chunk (byte-wise head, 8-lane bulk, byte-wise tail)"""
     eng = engine()
     msg = orc.fill(40_001, 7)
-    for l in (16, 32, 64, 128, 144, 192, 256):
+    for l in range(16, 257, 16):
         want = orc.bashHash(l, msg)
         assert eng.bashHash(l, msg) == want, l
         assert eng.bashHash(l, msg[:4096]) == orc.bashHash(l, msg[:4096]), l

@@ -26,11 +26,15 @@ def test_fused_kernel_shapes(orc, golden, l, msg_len):
     _check(eng, orc, golden.H[128:160], msg_len, 67, l)
 
 
-@pytest.mark.parametrize("msg_len", [1, 13, 15, 17, 100, 191, 193, 1000])
+@pytest.mark.parametrize("msg_len", [0, 1, 13, 15, 17, 100, 191, 193, 1000])
 def test_generic_kernel_ragged_lengths(orc, golden, msg_len):
     eng = engine()
     _check(eng, orc, golden.H[128:160], msg_len, 33, 256)
     _check(eng, orc, golden.H[160:176], msg_len, 5, 64)          # 128-bit key, low level
+    if msg_len in (0, 100, 193):                                 # the other fourteen levels: every sponge rate of the per-message path
+        for l in range(16, 257, 16):
+            if l not in (64, 256):
+                _check(eng, orc, golden.H[128:160], msg_len, 5, l, seed=l)
 
 
 def test_hash_only_and_mac_only(orc, golden):
