@@ -509,6 +509,61 @@ void bign_generic_sign_tail_kernel(const uint8_t *__restrict__ hashes, const uin
     codes[idx] = ct_sel(ok, (uint32_t)ERR_OK, st);
 }
 
+#ifdef BEE2HIP_EXPERIMENTS
+// --------------------------------------------------------- debug / self-test ---
+// bee2hip_debug_feG (include/bee2hip_internal.h): the device functions above, element-wise, over a caller-supplied modulus,
+// for tests/test_gpu_bign_generic_field.py.  Field ops take N limbs per item, point ops 3 N (X, Y, Z), all as the kernels
+// hold them (Montgomery domain except for the input of op 4).  op: 0 g_mul, 1 g_add, 2 g_sub, 3 g_inv, 4 x r2 (into the
+// Montgomery domain), 5 x 1 (out of it), 6 gj_dbl(a), 7 gj_add(a, b), 8 gp_add_complete(a, b), 9 gp_add_complete(a, a)
+// in place, as the ladder doubles.
+template <int N>
+__global__ __launch_bounds__(64)
+void bign_debug_feG_kernel(int op, const uint32_t *a, const uint32_t *b, uint32_t *out, size_t n, GenCurve<N> C)
+{
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    if (op < 6) {
+        gfe<N> x, y, r;
+        for (int i = 0; i < N; ++i) { x.v[i] = a[N * idx + i]; y.v[i] = b ? b[N * idx + i] : 0u; }
+        switch (op) {
+        case 0: g_mul(r, x, y, C); break;
+        case 1: g_add(r, x, y, C); break;
+        case 2: g_sub(r, x, y, C); break;
+        case 3: g_inv(r, x, C); break;
+        case 4: g_set(y, C.r2); g_mul(r, x, y, C); break;
+        default: for (int i = 0; i < N; ++i) y.v[i] = i == 0; g_mul(r, x, y, C); break;
+        }
+        for (int i = 0; i < N; ++i) out[N * idx + i] = r.v[i];
+        return;
+    }
+    uint32_t w[2][3 * N];
+    for (int i = 0; i < 3 * N; ++i) { w[0][i] = a[3 * N * idx + i]; w[1][i] = b ? b[3 * N * idx + i] : 0u; }
+    if (op < 8) {
+        gjac<N> T, E;
+        for (int i = 0; i < N; ++i) {
+            T.X.v[i] = w[0][i]; T.Y.v[i] = w[0][N + i]; T.Z.v[i] = w[0][2 * N + i];
+            E.X.v[i] = w[1][i]; E.Y.v[i] = w[1][N + i]; E.Z.v[i] = w[1][2 * N + i];
+        }
+        if (op == 6) gj_dbl(T, C); else gj_add(T, E, C);
+        for (int i = 0; i < N; ++i) { w[0][i] = T.X.v[i]; w[0][N + i] = T.Y.v[i]; w[0][2 * N + i] = T.Z.v[i]; }
+    } else {
+        gproj<N> P, Q;
+        for (int i = 0; i < N; ++i) {
+            P.X.v[i] = w[0][i]; P.Y.v[i] = w[0][N + i]; P.Z.v[i] = w[0][2 * N + i];
+            Q.X.v[i] = w[1][i]; Q.Y.v[i] = w[1][N + i]; Q.Z.v[i] = w[1][2 * N + i];
+        }
+        gfe<N> ca, b3, t;
+        g_set(ca, C.a);
+        g_set(t, C.b);
+        g_add(b3, t, t, C);
+        g_add(b3, b3, t, C);
+        if (op == 8) gp_add_complete(P, P, Q, ca, b3, C); else gp_add_complete(P, P, P, ca, b3, C);
+        for (int i = 0; i < N; ++i) { w[0][i] = P.X.v[i]; w[0][N + i] = P.Y.v[i]; w[0][2 * N + i] = P.Z.v[i]; }
+    }
+    for (int i = 0; i < 3 * N; ++i) out[3 * N * idx + i] = w[0][i];
+}
+#endif   // BEE2HIP_EXPERIMENTS
+
 // ------------------------------------------------------------------ host side ---
 namespace {
 // little multi-precision helpers on N 32-bit limbs (host; run once per call on the parameter set)
@@ -743,5 +798,49 @@ err_t launch_bign_sign_generic(const bign_params *params, int mode, const uint8_
     if (params->l == 256) return sign_generic_t<16>(params, mode, oid_der, oid_len, d_hashes, d_privkeys, d_aux, t_len, t_shared, n, d_sigs, d_codes, st);
     return ERR_BAD_PARAMS;
 }
+
+#ifdef BEE2HIP_EXPERIMENTS
+namespace {
+// the context of the hook comes from the product's own builders: make_mod (what the signing tail uses for q) for the ops
+// that need only p, n0, one and r2; make_curve (what every other kernel uses) for g_inv and the point ops, and for any op
+// with 0x100 set, so that both copies of the n0 / one / r2 derivation are reachable with any modulus
+template <int N>
+err_t debug_feG_t(int op, const octet *m, const octet *a, const octet *b, const void *d_a, const void *d_b, void *d_out, size_t n,
+                  hipStream_t st)
+{
+    constexpr int NO = 4 * N;
+    if (!(m[0] & 1) || !(m[NO - 1] & 0x80)) return ERR_BAD_PARAMS;
+    const int o = op & 0xFF;
+    if (o > 9 || (op & ~0x1FF)) return ERR_BAD_INPUT;
+    GenCurve<N> C;
+    if ((op & 0x100) || o == 3 || o >= 6) {
+        bign_params prm;
+        memset(&prm, 0, sizeof prm);
+        prm.l = 16 * N;
+        memcpy(prm.p, m, NO);
+        memcpy(prm.q, m, NO);
+        if (a) memcpy(prm.a, a, NO);
+        if (b) memcpy(prm.b, b, NO);
+        const err_t code = make_curve<N>(C, &prm);
+        if (code != ERR_OK) return code;
+    } else
+        make_mod<N>(C, m);
+    if (n == 0) return ERR_OK;
+    hipLaunchKernelGGL(bign_debug_feG_kernel<N>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, o, (const uint32_t *)d_a,
+                       (const uint32_t *)d_b, (uint32_t *)d_out, n, C);
+    B2H_TRY(hipGetLastError());
+    return ERR_OK;
+}
+}  // namespace
+err_t launch_bign_debug_feG(size_t l, int op, const octet *m, const octet *a, const octet *b, const void *d_a, const void *d_b,
+                            void *d_out, size_t n, hipStream_t st)
+{
+    if (!m || !d_a || !d_out) return ERR_BAD_INPUT;
+    if (l == 128) return debug_feG_t<8>(op, m, a, b, d_a, d_b, d_out, n, st);
+    if (l == 192) return debug_feG_t<12>(op, m, a, b, d_a, d_b, d_out, n, st);
+    if (l == 256) return debug_feG_t<16>(op, m, a, b, d_a, d_b, d_out, n, st);
+    return ERR_BAD_PARAMS;
+}
+#endif   // BEE2HIP_EXPERIMENTS
 
 }  // namespace bee2hip

@@ -849,5 +849,10 @@ extern "C" err_t bee2hip_debug_feL(size_t l, int op, const void *d_a, const void
 try {
     return launch_bign_debug_fe(l, op, d_a, d_b, d_out, n, as_stream(stream));
 } B2H_CATCH
+extern "C" err_t bee2hip_debug_feG(size_t l, int op, const octet m[64], const octet a[64], const octet b[64], const void *d_a,
+                                   const void *d_b, void *d_out, size_t n, void *stream)
+try {
+    return launch_bign_debug_feG(l, op, m, a, b, d_a, d_b, d_out, n, as_stream(stream));
+} B2H_CATCH
 #endif
 

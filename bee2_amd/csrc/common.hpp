@@ -107,5 +107,7 @@ err_t launch_bign_sign(size_t l, int mode, const uint8_t *oid_der, size_t oid_le
                        const void *d_privkeys, const void *d_aux, size_t t_len, int t_shared, size_t n, void *d_sigs,
                        void *d_codes, hipStream_t st);
 err_t launch_bign_debug_fe(size_t l, int op, const void *a, const void *b, void *out, size_t n, hipStream_t st);
+err_t launch_bign_debug_feG(size_t l, int op, const octet *m, const octet *a, const octet *b, const void *d_a, const void *d_b,
+                            void *d_out, size_t n, hipStream_t st);
 
 }  // namespace bee2hip

@@ -98,7 +98,7 @@ BATCH_SYMBOLS = [
     "bee2hip_set_device", "bee2hip_sync", "bee2hip_last_error", "bee2hip_version", "bee2hip_path_policy", "bee2hip_path_count",
 ]
 # include/bee2hip_internal.h: test / bench hooks, not product ABI
-INTERNAL_SYMBOLS = ["bee2hip_time_kernel", "bee2hip_debug_fe", "bee2hip_debug_feL", "bee2hip_internal_tune",
+INTERNAL_SYMBOLS = ["bee2hip_time_kernel", "bee2hip_debug_fe", "bee2hip_debug_feL", "bee2hip_debug_feG", "bee2hip_internal_tune",
                     "bee2hip_internal_clock_probe", "bee2hip_internal_stat"]
 
 
@@ -686,6 +686,14 @@ class Engine:
         self._check(self.lib.bee2hip_bignSignKL_batch_dev(
             _sz(l), bytes(oid_der), _sz(len(oid_der)), self._ptr(hashes), self._ptr(privkeys), self._ptr(ks), _sz(n),
             self._ptr(sigs), self._ptr(codes), self._stream()), "bignSignKL_batch_dev")
+
+    def debug_feG(self, l, op, m, a, b, ta, tb, tout, n):
+        """include/bee2hip_internal.h (libbee2hip_exp.so only): the generic-curve field / point arithmetic over the modulus m
+        (64 octets), element-wise on int32 CUDA tensors; returns the call's code"""
+        return self.lib.bee2hip_debug_feG(_sz(l), int(op), bytes(m), bytes(a) if a is not None else None,
+                                          bytes(b) if b is not None else None, self._ptr(ta),
+                                          self._ptr(tb) if tb is not None else None, self._ptr(tout), _sz(n), self._stream())
+
 
 
 _engine = None

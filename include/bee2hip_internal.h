@@ -29,6 +29,15 @@ err_t bee2hip_debug_fe(int op, const void *d_a, const void *d_b, void *d_out, si
 /* same over GF(2^(2l) - c) for l in {128, 192, 256} (8 / 12 / 16 limbs per element) */
 err_t bee2hip_debug_feL(size_t l, int op, const void *d_a, const void *d_b, void *d_out, size_t n,
                         void *stream);
+/* the arithmetic of the NON-STANDARD parameter sets (bign_generic_kernels.hip: Montgomery form on 32-bit limbs) over a
+   caller-supplied odd 2l-bit modulus m, element-wise on device arrays; the context (n0, R, R^2) comes from the builders
+   the product kernels use, the coefficients a (and b, for ops 8 / 9) are plain values < m, may be null for the field ops.
+   op: 0 a b R^-1, 1 a + b, 2 a - b, 3 a^(m-2) (Montgomery in and out, m prime), 4 a R (into the Montgomery domain),
+   5 a R^-1 (out of it): l / 32 limbs per item; 6 Jacobian doubling of a, 7 Jacobian a + b, 8 complete projective a + b,
+   9 complete projective a + a in place: triples X, Y, Z of 3 l / 32 limbs per item, Montgomery domain.
+   op | 0x100: the field ops with the context builder of the curve kernels instead of that of the signing tail */
+err_t bee2hip_debug_feG(size_t l, int op, const octet m[64], const octet a[64], const octet b[64], const void *d_a,
+                        const void *d_b, void *d_out, size_t n, void *stream);
 
 /* one wavefront spins for `us` microseconds on `stream` and writes {shader cycles, 100 MHz ticks} to d_out16:
    the clock the chip sustains under whatever runs beside it */

@@ -111,9 +111,11 @@ static inline hipError_t hipMalloc(void **p, size_t n)
 }
 static inline hipError_t hipDeviceSynchronize()
 {
-    std::vector<mockhip::Stream *> all;
-    { std::lock_guard<std::mutex> lk(mockhip::g().mu); all = mockhip::g().streams; }
-    for (mockhip::Stream *s : all) s->drain();
+    // the registry stays locked while its streams drain: hipStreamDestroy on another thread (legal beside a hipFree, and the
+    // library does it) takes the same lock before it deletes a stream, so none goes away under drain().  No queued task
+    // takes this lock, so the wait cannot hold one up.
+    std::lock_guard<std::mutex> lk(mockhip::g().mu);
+    for (mockhip::Stream *s : mockhip::g().streams) s->drain();
     return hipSuccess;
 }
 static inline hipError_t hipFree(void *p) { if (p) { hipDeviceSynchronize(); free(p); mockhip::g().live_device_blocks.fetch_sub(1); } return hipSuccess; }

@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE: pure-Python restatement of bignVerify / bignPubkeyVal over an ARBITRARY parameter set
+"""TEST INFRASTRUCTURE: pure-Python restatement of bignVerify / bignPubkeyVal / bignPubkeyCalc / bignSign over an ARBITRARY parameter set
 (bign_sign.c:268-361, bign_misc.c:319-365, bign_params.c:244-280, bign_ec.c:29-80), big integers and textbook affine
 formulas; belt-hash comes from the C oracle (orclib).  Pinned by tests/test_oracle_golden.py against
 tests/golden/bign_generic.json, which the reference itself produced (tools/make_golden_generic.py)."""
@@ -54,9 +54,9 @@ def _add(P1, P2, a, p):
     if x1 == x2:
         if (y1 + y2) % p == 0:
             return None
-        lam = (3 * x1 * x1 + a) * pow(2 * y1, p - 2, p) % p
+        lam = (3 * x1 * x1 + a) * pow(2 * y1, -1, p) % p
     else:
-        lam = (y2 - y1) * pow(x2 - x1, p - 2, p) % p
+        lam = (y2 - y1) * pow(x2 - x1, -1, p) % p
     x3 = (lam * lam - x1 - x2) % p
     return x3, (lam * (x1 - x3) - y1) % p
 
@@ -105,3 +105,84 @@ def pubkey_val(P, pub):
     if x >= p or y >= p:
         return ERR_BAD_PUBKEY
     return ERR_OK if (y * y - (x * x * x + a * x + b)) % p == 0 else ERR_BAD_PUBKEY
+
+
+ERR_BAD_RNG, ERR_BAD_PRIVKEY = 304, 504
+
+
+def pubkey_calc(P, priv):
+    """bignPubkeyCalc (bign_misc.c:373-429): ERR_BAD_PRIVKEY unless 0 < d < q, then Q = d G by affine arithmetic
+    (ERR_BAD_PARAMS if that is O).  Returns (code, pubkey)."""
+    code = params_check(P)
+    if code:
+        return code, b""
+    no = P.l // 4
+    p, a, q, yG = le(P.p[:no]), le(P.a[:no]), le(P.q[:no]), le(P.yG[:no])
+    d = le(priv[:no])
+    if d == 0 or d >= q:
+        return ERR_BAD_PRIVKEY, b""
+    Q = mul(d, (0, yG), a, p)
+    if Q is None:
+        return ERR_BAD_PARAMS, b""
+    return ERR_OK, Q[0].to_bytes(no, "little") + Q[1].to_bytes(no, "little")
+
+
+def sign_k(P, oid_der, h, priv, k, belt_hash):
+    """bignSign once its generator has produced the one-time key k (bign_sign.c:76-115): ERR_BAD_PRIVKEY unless 0 < d < q,
+    ERR_BAD_RNG unless 0 < k < q (zzRandNZMod accepts exactly that range), R = k G, s0 = belt-hash(oid || x_R || H) cut to
+    l bits, s1 = (k - (s0 + 2^l) d - H) mod q with H reduced by one subtraction.  Returns (code, sig)."""
+    code = params_check(P)
+    if code:
+        return code, b""
+    l = P.l
+    no = l // 4
+    p, a, q, yG = le(P.p[:no]), le(P.a[:no]), le(P.q[:no]), le(P.yG[:no])
+    d, kk = le(priv[:no]), le(k[:no])
+    if d == 0 or d >= q:
+        return ERR_BAD_PRIVKEY, b""
+    if kk == 0 or kk >= q:
+        return ERR_BAD_RNG, b""
+    R = mul(kk, (0, yG), a, p)
+    if R is None:
+        return ERR_BAD_PARAMS, b""
+    s0 = belt_hash(bytes(oid_der) + R[0].to_bytes(no, "little") + bytes(h[:no]))[:no // 2]
+    H = le(h[:no])
+    if H >= q:
+        H -= q
+    s1 = (kk - (le(s0) + (1 << l)) * d - H) % q
+    return ERR_OK, s0 + s1.to_bytes(no, "little")
+
+
+def ladder_events(P, h, sig, pub):
+    """The verification kernel's simultaneous double-and-add (bign_generic_verify_kernel: for i = 2l - 1 .. 0: T <- 2 T;
+    T <- T + G if bit i of u; T <- T + Q if i <= l and bit i of v) replayed on affine points, recording which exceptional
+    branch of the kernel's point arithmetic each step takes: "dbl Y == 0" (gj_dbl on a point of order 2), "add T == E"
+    (gj_add falls into the doubling), "add T == -E" (gj_add returns O), "R == O" (the result), each with the bit index i of the step (-1
+    for the result), in order.  Additions into or of O and doublings of O are ordinary early returns and are not recorded."""
+    l = P.l
+    no = l // 4
+    p, a, q, yG = le(P.p[:no]), le(P.a[:no]), le(P.q[:no]), le(P.yG[:no])
+    Q = (le(pub[:no]), le(pub[no:2 * no]))
+    s0, s1 = le(sig[:no // 2]), le(sig[no // 2:no // 2 + no])
+    H = le(h[:no])
+    if H >= q:
+        H -= q
+    u, v = (s1 + H) % q, s0 + (1 << l)
+    ev = []
+
+    def add(T, E, i):
+        if T is not None and E is not None and T[0] == E[0]:
+            ev.append(("add T == E" if T[1] == E[1] and T[1] else "add T == -E", i))
+        return _add(T, E, a, p)
+    T = None
+    for i in reversed(range(2 * l)):
+        if T is not None and T[1] == 0:
+            ev.append(("dbl Y == 0", i))
+        T = _add(T, T, a, p)
+        if (u >> i) & 1:
+            T = add(T, (0, yG), i)
+        if i <= l and (v >> i) & 1:
+            T = add(T, Q, i)
+    if T is None:
+        ev.append(("R == O", -1))
+    return ev

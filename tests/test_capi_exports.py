@@ -71,12 +71,15 @@ def _kernel_set(path):
 
 def test_experiments_library_holds_the_product_kernels_and_the_hook_kernels(lib_path):
     """libbee2hip_exp.so is the product plus test hooks: its kernels are exactly the product's and the kernels of the
-    hooks of include/bee2hip_internal.h (bee2hip_debug_fe{,L}: bign_debug_fe_kernel per curve; bee2hip_internal_clock_probe)"""
+    hooks of include/bee2hip_internal.h (bee2hip_debug_fe{,L}: bign_debug_fe_kernel per curve; bee2hip_debug_feG: bign_debug_feG_kernel
+    per size; bee2hip_internal_clock_probe)"""
     if not os.path.exists(E.EXP_LIB_PATH):
         pytest.skip("libbee2hip_exp.so not built")
     prod, exp = _kernel_set(lib_path), _kernel_set(E.EXP_LIB_PATH)
     hooks = {f"bee2hip::bign_debug_fe_kernel<{n}>(int, unsigned int const*, unsigned int const*, unsigned int*, unsigned long)"
              for n in (8, 12, 16)} | {"clock_probe_kernel(unsigned long long*, unsigned long long)"}
+    hooks |= {f"bee2hip::bign_debug_feG_kernel<{n}>(int, unsigned int const*, unsigned int const*, unsigned int*, unsigned long, "
+              f"bee2hip::GenCurve<{n}>)" for n in (8, 12, 16)}          # bee2hip_debug_feG
     assert not (prod & hooks)
     assert exp == prod | hooks, (sorted(exp - prod - hooks), sorted((prod | hooks) - exp))
 

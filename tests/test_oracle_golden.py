@@ -337,3 +337,78 @@ def test_generic_parameter_sets_python_restatement_vs_reference_fixtures(orc):
         h, s, k = (bytes.fromhex(c[x]) for x in ("hash", "sig", "pubkey"))
         assert OG.verify(P, bytes.fromhex(c["oid"]), h, s, k, orc.belt_hash) == c["verify"], c["name"]
         assert OG.pubkey_val(P, k) == c["pubkey_val"], c["name"]
+
+
+def test_generic_sign_k_and_pubkey_calc_python_restatement_vs_reference_fixtures(orc):
+    """orc_generic.pubkey_calc / sign_k (the checkers of the general-curve signing kernels on sets the reference cannot sign
+    on) against what the reference produced: the pubkey_calc and sign records of tests/golden/bign_generic_sign.json (the
+    one-time key of a sign record is the first draw of its recorded generator stream that lies in 1 .. q - 1, as
+    zzRandNZMod takes it) and the "by": "reference" records of tests/golden/bign_generic_adv.json"""
+    import json
+    import os
+    import orc_generic as OG
+    here = os.path.join(os.path.dirname(__file__), "golden")
+    G = json.load(open(os.path.join(here, "bign_generic.json")))
+    n = 0
+    for ent in json.load(open(os.path.join(here, "bign_generic_sign.json"))):
+        P = OG.Params.from_hex(G["curves"][ent["curve"]])
+        no = P.l // 4
+        q = OG.le(P.q[:no])
+        for x in ent["pubkey_calc"]:
+            code, pub = OG.pubkey_calc(P, bytes.fromhex(x["priv"]))
+            assert (code, pub.hex()) == (x["code"], x["pub"]), x["priv"]
+        for x in ent["sign"]:
+            stream = bytes.fromhex(x["rnd"])
+            draws = [stream[i: i + no] for i in range(0, len(stream), no)]
+            k = [d for d in draws if 0 < OG.le(d) < q][0]
+            code, sig = OG.sign_k(P, bytes.fromhex(x["oid"]), bytes.fromhex(x["hash"]), bytes.fromhex(x["priv"]), k, orc.belt_hash)
+            assert (code, sig.hex()) == (x["code"], x["sig"]), x
+            assert x["used"] == (0 if code else no * (draws.index(k) + 1))
+            n += 1
+    A = json.load(open(os.path.join(here, "bign_generic_adv.json")))
+    PP = [OG.Params.from_hex(s) for s in A["sets"]]
+    for x in A["pubkey_calc"]:
+        if x["by"] == "reference":
+            assert OG.pubkey_calc(PP[x["set"]], bytes.fromhex(x["priv"])) == (x["code"], bytes.fromhex(x["pub"]))
+            n += 1
+    codes = set()
+    for x in A["sign_k"]:
+        if x["by"] == "reference":
+            got = OG.sign_k(PP[x["set"]], *(bytes.fromhex(x[f]) for f in ("oid", "hash", "priv", "k")), orc.belt_hash)
+            assert got == (x["code"], bytes.fromhex(x["sig"])), x
+            codes.add(x["code"])
+            n += 1
+    assert codes == {0, 504} and n > 60          # a refused k has no reference record: its generator would be asked again
+
+
+def test_generic_adversarial_fixture_python_restatement(orc):
+    """every expected value of tests/golden/bign_generic_adv.json recomputed with tests/orc_generic.py: the verdicts on the
+    adversarial parameter sets (valid no-wrap signatures, their corruptions, the crafted exceptional cases -- the tool took
+    each code from the reference), the public keys and signatures of the signing side; and the affine model of the
+    verification ladder names, for each crafted case, the branch the case is there for"""
+    import json
+    import os
+    import orc_generic as OG
+    A = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "bign_generic_adv.json")))
+    PP = [OG.Params.from_hex(s) for s in A["sets"]]
+    assert len(PP) == 27 and all(OG.params_check(P) == 0 for P in PP)
+    assert {(s["l"], s["kind"]) for s in A["sets"]} == {(l, k) for l in (128, 192, 256) for k in ("adv", "tors", "iso")}
+    assert {s["q_kind"] for s in A["sets"]} == {"2^(2l) - 1", "2^(2l-1) + 1", "low limb 1", "random odd", "standard"}
+    for x in A["verify"] + A["crafted"]:
+        got = OG.verify(PP[x["set"]], *(bytes.fromhex(x[f]) for f in ("oid", "hash", "sig", "pubkey")), orc.belt_hash)
+        assert got == x["code"], (x["set"], x["name"])
+    event = {"T == E": "add T == E", "T == -E": "add T == -E", "T == E later": "add T == E", "Y == 0 doubling": "dbl Y == 0", "R == O": "R == O"}
+    seen = set()
+    for x in A["crafted"]:
+        P = PP[x["set"]]
+        ev = OG.ladder_events(P, *(bytes.fromhex(x[f]) for f in ("hash", "sig", "pubkey")))
+        hit = [i for e, i in ev if e == event[x["name"]]]
+        assert hit and (x["name"] in ("Y == 0 doubling", "R == O") or P.l in hit), (x["name"], ev)
+        assert (x["name"] == "T == E later") == (ev[0] == ("add T == E", P.l) and int(x["pubkey"][:P.l // 2], 16) != 0)    # Q = 2 G, not G
+        seen.add((P.l, x["name"]))
+    assert seen == {(l, n) for l in (128, 192, 256) for n in event}
+    for x in A["pubkey_calc"]:
+        assert OG.pubkey_calc(PP[x["set"]], bytes.fromhex(x["priv"])) == (x["code"], bytes.fromhex(x["pub"]))
+    for x in A["sign_k"]:
+        got = OG.sign_k(PP[x["set"]], *(bytes.fromhex(x[f]) for f in ("oid", "hash", "priv", "k")), orc.belt_hash)
+        assert got == (x["code"], bytes.fromhex(x["sig"])), x

@@ -278,3 +278,45 @@ def test_generic_parameter_fixtures_are_what_the_reference_says():
         h, s, k = (bytes.fromhex(c[x]) for x in ("hash", "sig", "pubkey"))
         assert L.bignVerify(ctypes.byref(prm), oid, ctypes.c_size_t(len(oid)), h, s, k) & 0xFFFFFFFF == c["verify"], c["name"]
         assert L.bignPubkeyVal(ctypes.byref(prm), k) & 0xFFFFFFFF == c["pubkey_val"], c["name"]
+
+
+def test_generic_adversarial_fixtures_are_what_the_reference_says():
+    """tests/golden/bign_generic_adv.json replayed through the compiled reference: every verdict on the adversarial parameter
+    sets (the special q's among them, which the reference accepts: bignParamsCheck does not ask for a prime q), the crafted
+    exceptional cases, and the signing-side records the reference produced (bignPubkeyCalc; bignSign with a generator that
+    replays the one-time key)"""
+    import json
+    import make_golden_sign as MS
+    from bee2_amd.engine import bign_params
+    L = refgen.ref()
+    d = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "bign_generic_adv.json")))
+
+    def mk(c):
+        prm = bign_params()
+        prm.l = c["l"]
+        for f in ("p", "a", "b", "q", "yG"):
+            raw = bytes.fromhex(c[f])
+            ctypes.memmove(getattr(prm, f), raw + bytes(64 - len(raw)), 64)
+        return prm
+    P = [mk(c) for c in d["sets"]]
+    for c in d["verify"] + d["crafted"]:
+        oid = bytes.fromhex(c["oid"])
+        got = L.bignVerify(ctypes.byref(P[c["set"]]), oid, _sz(len(oid)), bytes.fromhex(c["hash"]), bytes.fromhex(c["sig"]),
+                           bytes.fromhex(c["pubkey"])) & 0xFFFFFFFF
+        assert got == c["code"], (c["set"], c["name"])
+    n = 0
+    for c in d["pubkey_calc"]:
+        if c["by"] == "reference":
+            pub = ctypes.create_string_buffer(len(c["priv"]))
+            code = L.bignPubkeyCalc(pub, ctypes.byref(P[c["set"]]), bytes.fromhex(c["priv"])) & 0xFFFFFFFF
+            assert code == c["code"] and (code or pub.raw.hex() == c["pub"]), c["priv"]
+            n += 1
+    for c in d["sign_k"]:
+        if c["by"] == "reference":
+            oid = bytes.fromhex(c["oid"])
+            sig = ctypes.create_string_buffer(3 * len(c["priv"]) // 4)
+            code = L.bignSign(sig, ctypes.byref(P[c["set"]]), oid, _sz(len(oid)), bytes.fromhex(c["hash"]), bytes.fromhex(c["priv"]),
+                              MS.replay(bytes.fromhex(c["k"])), None) & 0xFFFFFFFF
+            assert code == c["code"] and (code or sig.raw.hex() == c["sig"]), c
+            n += 1
+    assert n == 3 * (9 + 8)
