@@ -23,6 +23,7 @@
  */
 #include "oracle.h"
 #include "orc_threads.h"
+#include <stdlib.h>
 #include <string.h>
 
 typedef unsigned __int128 u128;
@@ -660,11 +661,13 @@ uint32_t orc_bignSign2(size_t l, uint8_t *sig, const uint8_t *oid_der, size_t oi
     {
         uint8_t stack_msg[ORC_OID_MAX + 64 + 256];
         msg = stack_msg;
-        if (t_len > 256) return ORC_BAD_INPUT;                     /* checker limit, not the reference's */
+        if (!t) t_len = 0;
+        if (t_len > 256 && !(msg = (uint8_t *)malloc(ORC_OID_MAX + 64 + t_len))) return ORC_BAD_INPUT;   /* (any length, as the reference) */
         memcpy(msg, oid_der, oid_len);
         memcpy(msg + oid_len, privkey, no);
-        if (t) memcpy(msg + oid_len + no, t, t_len);
-        orc_beltHash(theta, msg, oid_len + no + (t ? t_len : 0));
+        if (t_len) memcpy(msg + oid_len + no, t, t_len);
+        orc_beltHash(theta, msg, oid_len + no + t_len);
+        if (msg != stack_msg) { memset(msg, 0, oid_len + no + t_len); free(msg); }
     }
     /* k = H; k <- belt-wbl_theta(k) until k in {1..q-1} (:203-216) */
     orc_beltKeyExpand2(K, theta, 32);

@@ -247,6 +247,82 @@ def test_device_batch_sign_verify_pipeline_2pow16(orc, n):
     assert orc.sign2(l, oid, hh[:no], hp[:no], ht[:8]) == (0, host(sigs)[:sg])
 
 
+def _sign_inputs(orc, eng, l, n, seed):
+    """seeded keys and hashes with two refused keys (0 and q) mixed in -> (P, q, privs, hashes, refused indices)"""
+    P = _params(eng, l)
+    no = l // 4
+    q = int.from_bytes(bytes(P.q)[:no], "little")
+    privs = bytearray(orc.fill(no * n, seed + l))
+    for i in range(n):
+        privs[no * (i + 1) - 1] &= 0x7F                                  # below q: only the two keys planted here are refused
+    refused = (5, 40)
+    privs[no * 5: no * 6] = bytes(no)
+    privs[no * 40: no * 41] = q.to_bytes(no, "little")
+    return P, q, bytes(privs), orc.fill(no * n, seed + 0x100 + l), refused
+
+
+@pytest.mark.parametrize("l", [128, 192, 256])
+def test_batch_signing_hashes_long_additional_input_in_one_secret_launch(orc, l):
+    """bee2hip_bignSign2_batch with a shared t of more than 64 octets (capi_bign.hip, sign_batch_host): theta = belt-hash(oid || d || t)
+    of all n items in ONE launch of belt_hash_ragged_kernel<BeltTabTwoP, 256> with long_from = ~0 -- item i at i * ml, so with ml odd
+    the lanes of a wavefront start at all 16 alignments (tests/test_ragged_grid.py proves it for these t_len); t of 4097 and 5000
+    octets are messages of 4 KiB and more that THIS kernel walks itself.  1 .. 64 octets beside them: the nonce kernel assembles the
+    message itself, 64 / 65 is the boundary between the two.  67 items, keys 0 and q refused: codes and signatures per item as the
+    oracle, slots of refused items untouched, and the batch verifies on the device."""
+    import raggedgrid as RG
+    eng = engine()
+    n, no, sg = RG.SIGN_N, l // 4, 3 * l // 8
+    oid = E.LEVEL_OID[l]
+    P, q, privs, hashes, refused = _sign_inputs(orc, eng, l, n, 0x7E7A)
+    code, pubs, pcodes = eng.bignPubkeyCalc_batch(P, privs)
+    assert code == 0 and [i for i in range(n) if pcodes[i]] == list(refused)
+    good = [i for i in range(n) if i not in refused]
+    vh = b"".join(hashes[no * i: no * (i + 1)] for i in good)
+    vp = b"".join(pubs[2 * no * i: 2 * no * (i + 1)] for i in good)
+    t_lens = list(RG.SIGN_T_SHARED) + [RG.SIGN_T_ODD[l]]
+    assert RG.sign_alignments(l, RG.SIGN_T_ODD[l]) == set(range(16))
+    seen = set()
+    for t_len in t_lens:
+        t = orc.fill(t_len, 0x7000 + t_len)
+        code, sigs, scodes = eng.bignSign2_batch(P, oid, hashes, privs, t)
+        assert code == 0, t_len
+        for i in range(n):
+            w = orc.sign2(l, oid, hashes[no * i: no * (i + 1)], privs[no * i: no * (i + 1)], t)
+            assert scodes[i] == w[0], (l, t_len, i)
+            assert (w[0] != 0) == (i in refused)
+            assert sigs[sg * i: sg * (i + 1)] == (w[1] if w[0] == 0 else bytes(sg)), (l, t_len, i, (i * RG.sign_ml(l, t_len)) % 16)
+        assert sigs not in seen                                          # (t enters the nonce: every t_len its own signatures)
+        seen.add(sigs)
+        code, vcodes = eng.bignVerify_batch(vh, b"".join(sigs[sg * i: sg * (i + 1)] for i in good), vp, oid_der=oid, params=P)
+        assert code == 0 and vcodes == [0] * len(good), (l, t_len)
+
+
+@pytest.mark.parametrize("l", [128, 192, 256])
+@pytest.mark.parametrize("shared", [False, True], ids=["per_item_t", "shared_t"])
+def test_device_signing_with_additional_input_up_to_its_limit(orc, l, shared):
+    """bee2hip_bignSign2L_batch_dev takes t of at most 64 octets (include/bee2hip.h) and the nonce kernel assembles oid || d || t
+    itself: t_len = 1, 31, 32, 33, 63 and 64, per item (item i's t at i * t_len: every start alignment for the odd ones) and
+    shared; 67 items with keys 0 and q refused -- codes and signatures as the oracle, signatures of refused items zero"""
+    import raggedgrid as RG
+    eng = engine()
+    n, no, sg = RG.SIGN_N, l // 4, 3 * l // 8
+    oid = E.LEVEL_OID[l]
+    P, q, privs, hashes, refused = _sign_inputs(orc, eng, l, n, 0xD7E7)
+    dp, dh = dev(privs), dev(hashes)
+    for t_len in RG.SIGN_T_DEV:
+        ts = orc.fill(t_len if shared else t_len * n, 0x7100 + t_len)
+        sigs = torch.full((sg * n,), 0xA5, dtype=torch.uint8, device="cuda")
+        codes = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+        eng.bignSign2L_batch_dev(l, oid, dh, dp, sigs, codes, t=dev(ts + bytes(-len(ts) % 4)), t_len=t_len, t_shared=shared)
+        torch.cuda.synchronize()
+        hs, hc = host(sigs), [int(c) & 0xFFFFFFFF for c in codes.cpu().numpy()]
+        for i in range(n):
+            t = ts if shared else ts[t_len * i: t_len * (i + 1)]
+            w = orc.sign2(l, oid, hashes[no * i: no * (i + 1)], privs[no * i: no * (i + 1)], t)
+            assert hc[i] == w[0] and (w[0] != 0) == (i in refused), (l, t_len, i)
+            assert hs[sg * i: sg * (i + 1)] == (w[1] if w[0] == 0 else bytes(sg)), (l, t_len, i)
+
+
 def test_misuse_and_argument_checks():
     """argument checks in the reference's order: parameters, pointers, OID, rng, private key"""
     eng = engine()

@@ -67,6 +67,27 @@ def test_bash_hash_random(orc):
         assert a.raw == orc.bashHash(l, msg)[1]
 
 
+def test_hashes_at_every_length_of_the_ragged_grids(orc):
+    """the expected values of tests/test_gpu_hash_ragged_grid.py come from the oracle: here the oracle's belt-hash and bash256 / 384 /
+    512 meet the reference on one message per distinct length of those grids (short and long sets, the fillers' 0..15, the 1..199
+    of the size-regime batches)"""
+    import raggedgrid as RG
+    L = refgen.ref()
+    rnd = random.Random(0x6419)
+    for alg in RG.ALGS:
+        lengths = sorted(set(RG.short_lengths(alg)) | set(RG.long_lengths(alg)) | set(range(200)))
+        assert set(RG.short_lengths(alg)) <= set(lengths) and set(RG.long_lengths(alg)) <= set(lengths)
+        for n in lengths:
+            msg = rnd.randbytes(n)
+            a = ctypes.create_string_buffer(RG.DIGEST[alg])
+            if alg == 0:
+                assert L.beltHash(a, msg, _sz(n)) == 0
+                assert a.raw == orc.belt_hash(msg), n
+            else:
+                assert L.bashHash(a, _sz(alg), msg, _sz(n)) == 0
+                assert a.raw == orc.bashHash(alg, msg)[1], (alg, n)
+
+
 def test_verify_random_and_corrupted(orc):
     rnd = random.Random(7)
     triples = refgen.make_triples(1500, 0x1234)
@@ -246,6 +267,15 @@ def test_sign2_pubkey_calc_random(orc):
             assert getattr(L, f"bign{l}Sign2")(want, h, priv, t, _sz(len(t) if t else 0)) == 0
             assert orc.sign2(l, oid[l], h, priv, t) == (0, want.raw)
             assert refgen.verify_l(l, h, want.raw, pub) == 0
+        # the additional inputs of the batch-signing cases (tests/raggedgrid.py): both sides of 64 octets, and the long ones for
+        # which the oracle assembles oid || d || t on the heap
+        import raggedgrid as RG
+        for t_len in list(RG.SIGN_T_SHARED) + [RG.SIGN_T_ODD[l]]:
+            priv, pub = refgen.keypair_l(l, rng)
+            h, t = rng.bytes(no), rnd.randbytes(t_len)
+            want = ctypes.create_string_buffer(sg)
+            assert getattr(L, f"bign{l}Sign2")(want, h, priv, t, _sz(t_len)) == 0
+            assert orc.sign2(l, oid[l], h, priv, t) == (0, want.raw), (l, t_len)
 
 
 def test_generic_parameter_fixtures_are_what_the_reference_says():
