@@ -12,6 +12,7 @@
 //   capi_belt.hip   belt block / CTR / MAC / modes / AEAD / belt-hash
 //   capi_bign.hip   bign verification, validation, key generation, signing
 //   capi_mixed.hip  bash + belt-MAC per message, ragged hash batches, path policy
+//   capi_prg.hip    bash-prg (prg-hash, prg-ae) over ragged batches
 //   capi_exp.hip    experiment hooks (libbee2hip_exp.so only)
 #include "staging.hpp"
 static const bool g_capture_query_set = (bee2hip::g_stream_capturing = bee2hip::stream_is_capturing, true);
@@ -20,4 +21,5 @@ static const bool g_capture_query_set = (bee2hip::g_stream_capturing = bee2hip::
 #include "capi_belt.hip"
 #include "capi_bign.hip"
 #include "capi_mixed.hip"
+#include "capi_prg.hip"
 #include "capi_exp.hip"

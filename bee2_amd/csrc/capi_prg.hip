@@ -1,0 +1,182 @@
+// capi_prg.hip -- bash-prg over ragged batches: prg-hash and prg-ae (STB 34.101.77 annexes A.5, A.6; src/crypto/bash/bash_prg.c).
+// Part of the C ABI (capi.hip).  One record = one automaton = one lane of bash_prg_ragged_kernel (bash_prg_kernels.hip).
+// bee2's own step functions (Start / Absorb / Encr ...) are NOT exported: one automaton is a serial chain, the batch is the product.
+
+// what bashPrgStart asserts (bash_prg.c:115-119) plus the limits of one squeeze; before any device work
+static err_t prg_check(size_t l, size_t d, const octet ann[], size_t ann_len, bool keyed, const octet key[], size_t key_len,
+                       size_t out_len, size_t n)
+{
+    if ((l != 128 && l != 192 && l != 256) || (d != 1 && d != 2)) return ERR_BAD_PARAMS;
+    if (ann_len % 4 != 0 || ann_len > 60) return ERR_BAD_INPUT;
+    if (keyed && (key_len % 4 != 0 || key_len < l / 8 || key_len > 60 || !key)) return ERR_BAD_INPUT;
+    if (!keyed && ann_len && !ann) return ERR_BAD_INPUT;
+    if (out_len < 1 || out_len > 64) return ERR_BAD_INPUT;
+    if (n > 0xffffffffull) return ERR_BAD_INPUT;
+    return ERR_OK;
+}
+
+static void prg_args(BashPrgArgs &A, uint32_t mode, size_t l, size_t d, const octet fixed[], size_t fixed_len, size_t own_ann_len,
+                     size_t out_len)
+{
+    memset(&A, 0, sizeof A);
+    if (fixed_len) memcpy(A.fixed, fixed, fixed_len);
+    A.n_fixed = (uint32_t)(fixed_len / 4);
+    A.n_ann = (uint32_t)(own_ann_len / 4);
+    const size_t ann_len = mode == BASH_PRG_HASH ? fixed_len : own_ann_len, key_len = mode == BASH_PRG_HASH ? 0 : fixed_len;
+    A.head = (uint32_t)(ann_len * 4 + key_len / 4);                                 // bash_prg.c:125
+    A.cap = (uint32_t)(l / 4 + d);                                                  // bash_prg.c:131
+    A.rate = (uint32_t)(key_len ? 192 - l * (2 + d) / 16 : 192 - d * l / 4);        // bash_prg.c:133
+    A.mode = mode;
+    A.out_len = (uint32_t)out_len;
+}
+
+extern "C" err_t bee2hip_bashPrgHash_ragged_stream(size_t l, size_t d, const octet ann[], size_t ann_len, const void *d_data,
+                                                   const void *d_offsets, const void *d_order, size_t n, void *d_out,
+                                                   size_t out_len, void *stream)
+try {
+    err_t code = prg_check(l, d, ann, ann_len, false, nullptr, 0, out_len, n);
+    if (code != ERR_OK) return code;
+    if (misaligned(d_offsets, 8) || misaligned(d_order, 4)) return ERR_BAD_INPUT;
+    if (n && (!d_offsets || !d_out)) return ERR_BAD_INPUT;
+    code = ensure_device();
+    if (code != ERR_OK) return code;
+    BashPrgArgs A;
+    prg_args(A, BASH_PRG_HASH, l, d, ann, ann_len, 0, out_len);
+    return launch_prg_ragged(A, nullptr, d_data, d_offsets, nullptr, nullptr, d_order, n, nullptr, d_out, nullptr, as_stream(stream));
+} B2H_CATCH
+
+extern "C" err_t bee2hip_bashPrgAE_ragged_stream(int unwrap, size_t l, size_t d, const octet key[], size_t key_len,
+                                                 const void *d_anns, size_t ann_len, const void *d_hdrs,
+                                                 const void *d_hdr_offsets, const void *d_src, const void *d_offsets,
+                                                 const void *d_order, size_t n, void *d_dst, void *d_tags, size_t tag_len,
+                                                 void *d_codes, void *stream)
+try {
+    err_t code = prg_check(l, d, nullptr, ann_len, true, key, key_len, tag_len, n);
+    if (code != ERR_OK) return code;
+    if (unwrap != 0 && unwrap != 1) return ERR_BAD_INPUT;
+    if (misaligned(d_offsets, 8) || misaligned(d_hdr_offsets, 8) || misaligned(d_order, 4) || misaligned(d_anns, 4) ||
+        misaligned(d_codes, 4))
+        return ERR_BAD_INPUT;
+    if (d_hdrs && !d_hdr_offsets) return ERR_BAD_INPUT;
+    if ((d_src == nullptr) != (d_dst == nullptr)) return ERR_BAD_INPUT;
+    if (n && (!d_offsets || !d_tags || (ann_len && !d_anns) || (unwrap && !d_codes))) return ERR_BAD_INPUT;
+    code = ensure_device();
+    if (code != ERR_OK) return code;
+    BashPrgArgs A;
+    prg_args(A, unwrap ? BASH_PRG_UNWRAP : BASH_PRG_WRAP, l, d, key, key_len, ann_len, tag_len);
+    return launch_prg_ragged(A, d_anns, d_hdrs, d_hdr_offsets, d_src, d_offsets, d_order, n, d_dst, d_tags, d_codes,
+                             as_stream(stream));
+} B2H_CATCH
+
+// ---- host-pointer entries: stage through t_scr[3], longest record first (a wavefront runs until its longest record is done),
+// one call of the stream entry on the NULL stream.  As hash_ragged_host without its host threads: a record's text has to come
+// back from wherever it was processed, so nothing is gained by keeping long ones here.
+static bool prg_offsets_ok(const uint64_t *offsets, size_t n)
+{
+    for (size_t i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i]) return false;
+    return true;
+}
+static void prg_longest_first(std::vector<uint32_t> &ord, const uint64_t *offsets, size_t n)
+{
+    ord.resize(n);
+    for (size_t i = 0; i < n; ++i) ord[i] = (uint32_t)i;
+    std::stable_sort(ord.begin(), ord.end(), [offsets](uint32_t a, uint32_t b) {
+        return offsets[a + 1] - offsets[a] > offsets[b + 1] - offsets[b];
+    });
+}
+static inline size_t prg_up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+extern "C" err_t bee2hip_bashPrgHash_ragged(size_t l, size_t d, const octet ann[], size_t ann_len, const octet *data,
+                                            const uint64_t *offsets, size_t n, octet *out, size_t out_len)
+try {
+    err_t code = prg_check(l, d, ann, ann_len, false, nullptr, 0, out_len, n);
+    if (code != ERR_OK) return code;
+    if (n == 0) return ERR_OK;
+    if (!offsets || !out || !prg_offsets_ok(offsets, n)) return ERR_BAD_INPUT;
+    const size_t first = (size_t)offsets[0], total = (size_t)(offsets[n] - offsets[0]);
+    if (total && !data) return ERR_BAD_INPUT;
+    code = ensure_device();
+    if (code != ERR_OK) return code;
+    std::vector<uint32_t> ord;
+    prg_longest_first(ord, offsets, n);
+    // the data keeps its alignment mod 16 (first & 15 octets of slack in front), offsets are rebased to the staging block
+    const size_t lead = first & 15, o_off = prg_up16(lead + total), o_ord = o_off + prg_up16((n + 1) * 8),
+                 o_out = o_ord + prg_up16(n * 4);
+    Scratch &s = t_scr[3];
+    code = s.need(o_out + n * out_len + 16);
+    if (code != ERR_OK) return code;
+    octet *dv = (octet *)s.p;
+    std::vector<uint64_t> off(n + 1);
+    for (size_t i = 0; i <= n; ++i) off[i] = offsets[i] - first + lead;
+    if (total) B2H_TRY(h2d(dv + lead, data + first, total));
+    B2H_TRY(h2d(dv + o_off, off.data(), (n + 1) * 8));
+    B2H_TRY(h2d(dv + o_ord, ord.data(), n * 4));
+    code = bee2hip_bashPrgHash_ragged_stream(l, d, ann, ann_len, dv, dv + o_off, dv + o_ord, n, dv + o_out, out_len, nullptr);
+    if (code != ERR_OK) return code;
+    B2H_TRY(d2h(out, dv + o_out, n * out_len));
+    return ERR_OK;
+} B2H_CATCH
+
+static err_t prg_ae_host(int unwrap, size_t l, size_t d, const octet key[], size_t key_len, const octet *anns, size_t ann_len,
+                         const octet *hdrs, const uint64_t *hdr_offsets, const octet *src, const uint64_t *offsets, size_t n,
+                         octet *dst, octet *tags, size_t tag_len, err_t *codes)
+{
+    err_t code = prg_check(l, d, nullptr, ann_len, true, key, key_len, tag_len, n);
+    if (code != ERR_OK) return code;
+    if (n == 0) return ERR_OK;
+    if (!offsets || !tags || (ann_len && !anns) || (unwrap && !codes) || (hdrs && !hdr_offsets)) return ERR_BAD_INPUT;
+    if (!prg_offsets_ok(offsets, n) || (hdr_offsets && !prg_offsets_ok(hdr_offsets, n))) return ERR_BAD_INPUT;
+    const size_t first = (size_t)offsets[0], total = (size_t)(offsets[n] - offsets[0]);
+    const size_t hfirst = hdr_offsets ? (size_t)hdr_offsets[0] : 0, htotal = hdr_offsets ? (size_t)(hdr_offsets[n] - hdr_offsets[0]) : 0;
+    if ((total && (!src || !dst)) || (htotal && !hdrs)) return ERR_BAD_INPUT;
+    code = ensure_device();
+    if (code != ERR_OK) return code;
+    std::vector<uint32_t> ord;
+    prg_longest_first(ord, offsets, n);
+    const size_t lead = first & 15, hlead = hfirst & 15;
+    const size_t o_hdr = prg_up16(lead + total), o_ann = o_hdr + prg_up16(hlead + htotal), o_off = o_ann + prg_up16(n * ann_len),
+                 o_hoff = o_off + prg_up16((n + 1) * 8), o_ord = o_hoff + prg_up16((n + 1) * 8), o_tag = o_ord + prg_up16(n * 4),
+                 o_code = o_tag + prg_up16(n * tag_len);
+    Scratch &s = t_scr[3];
+    code = s.need(o_code + n * 4 + 16);
+    if (code != ERR_OK) return code;
+    octet *dv = (octet *)s.p;
+    std::vector<uint64_t> off(n + 1);
+    for (size_t i = 0; i <= n; ++i) off[i] = offsets[i] - first + lead;
+    B2H_TRY(h2d(dv + o_off, off.data(), (n + 1) * 8));
+    if (hdr_offsets) {
+        for (size_t i = 0; i <= n; ++i) off[i] = hdr_offsets[i] - hfirst + hlead;
+        B2H_TRY(h2d(dv + o_hoff, off.data(), (n + 1) * 8));
+        if (htotal) B2H_TRY(h2d(dv + o_hdr + hlead, hdrs + hfirst, htotal));
+    }
+    if (total) B2H_TRY(h2d(dv + lead, src + first, total));
+    if (ann_len) B2H_TRY(h2d(dv + o_ann, anns, n * ann_len));
+    if (unwrap) B2H_TRY(h2d(dv + o_tag, tags, n * tag_len));
+    B2H_TRY(h2d(dv + o_ord, ord.data(), n * 4));
+    // in place on the device: the text is staged once
+    code = bee2hip_bashPrgAE_ragged_stream(unwrap, l, d, key, key_len, dv + o_ann, ann_len, hdr_offsets ? dv + o_hdr : nullptr,
+                                           hdr_offsets ? dv + o_hoff : nullptr, dv, dv + o_off, dv + o_ord, n, dv, dv + o_tag,
+                                           tag_len, unwrap ? dv + o_code : nullptr, nullptr);
+    if (code != ERR_OK) return code;
+    if (total) B2H_TRY(d2h(dst + first, dv + lead, total));
+    if (unwrap) B2H_TRY(d2h(codes, dv + o_code, n * 4));
+    else B2H_TRY(d2h(tags, dv + o_tag, n * tag_len));
+    return ERR_OK;
+}
+
+extern "C" err_t bee2hip_bashPrgAE_wrap_ragged(size_t l, size_t d, const octet key[], size_t key_len, const octet *anns,
+                                               size_t ann_len, const octet *hdrs, const uint64_t *hdr_offsets, const octet *src,
+                                               const uint64_t *offsets, size_t n, octet *dst, octet *tags, size_t tag_len)
+try {
+    return prg_ae_host(0, l, d, key, key_len, anns, ann_len, hdrs, hdr_offsets, src, offsets, n, dst, tags, tag_len, nullptr);
+} B2H_CATCH
+
+extern "C" err_t bee2hip_bashPrgAE_unwrap_ragged(size_t l, size_t d, const octet key[], size_t key_len, const octet *anns,
+                                                 size_t ann_len, const octet *hdrs, const uint64_t *hdr_offsets, const octet *src,
+                                                 const uint64_t *offsets, size_t n, const octet *tags, size_t tag_len, octet *dst,
+                                                 err_t *codes)
+try {
+    return prg_ae_host(1, l, d, key, key_len, anns, ann_len, hdrs, hdr_offsets, src, offsets, n, dst, const_cast<octet *>(tags),
+                       tag_len, codes);
+} B2H_CATCH

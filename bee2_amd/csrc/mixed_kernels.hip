@@ -783,7 +783,7 @@ void belt_hash_long_kernel(const uint8_t *__restrict__ data, const uint64_t *__r
 // their length, buckets in descending order (a counting sort: histogram, prefix, scatter).  Inside a
 // wavefront lengths then differ by less than 2x; the order inside a bucket is whatever the atomics
 // give -- it only decides which lane hashes which message, every digest lands at its own index.
-// work[0..63] = histogram, work[64..127] = bucket start, work[128..191] = cursor
+// work[0..63] = histogram, work[64..127] = cursor
 __device__ __forceinline__ unsigned ragged_bucket(uint64_t len) { return len ? 63u - (unsigned)__builtin_clzll(len) + 1u : 0u; }
 // (global atomics of 65 536 threads on ~19 addresses serialise -- 160 us per kernel; a workgroup therefore
 // counts in LDS first and touches each global bucket once)
@@ -798,27 +798,51 @@ void ragged_hist_kernel(const uint64_t *__restrict__ off, size_t n, unsigned *__
     __syncthreads();
     if (threadIdx.x < 64 && h[threadIdx.x]) atomicAdd(&work[threadIdx.x], h[threadIdx.x]);
 }
-__global__ void ragged_scan_kernel(unsigned *__restrict__ work)
-{
-    if (threadIdx.x || blockIdx.x) return;
-    unsigned acc = 0;
-    for (int b = 63; b >= 0; --b) { work[64 + b] = acc; work[128 + b] = 0; acc += work[b]; }
-}
+// Where a bucket starts = how many messages the longer buckets hold: a suffix sum over the 64 counts, which the first
+// wavefront of every workgroup takes for itself in six shuffle steps (it used to be a one-thread kernel between the two).
 __global__ __launch_bounds__(256)
 void ragged_scatter_kernel(const uint64_t *__restrict__ off, size_t n, unsigned *__restrict__ work,
                            uint32_t *__restrict__ order)
 {
-    __shared__ unsigned cnt[64], base[64];
-    if (threadIdx.x < 64) cnt[threadIdx.x] = 0;
+    __shared__ unsigned cnt[64], base[64], start[64];
+    if (threadIdx.x < 64) {
+        const unsigned b = threadIdx.x, own = work[b];
+        unsigned acc = own;                                               // -> own + every bucket above b
+#pragma unroll
+        for (unsigned d = 1; d < 64; d *= 2) {
+            const unsigned up = __shfl_down(acc, d, 64);
+            if (b + d < 64) acc += up;
+        }
+        start[b] = acc - own;
+        cnt[b] = 0;
+    }
     __syncthreads();
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned b = 0, rank = 0;
     if (i < n) { b = ragged_bucket(off[i + 1] - off[i]); rank = atomicAdd(&cnt[b], 1u); }
     __syncthreads();
     if (threadIdx.x < 64 && cnt[threadIdx.x])                         // this workgroup's slice of every bucket
-        base[threadIdx.x] = work[64 + threadIdx.x] + atomicAdd(&work[128 + threadIdx.x], cnt[threadIdx.x]);
+        base[threadIdx.x] = start[threadIdx.x] + atomicAdd(&work[64 + threadIdx.x], cnt[threadIdx.x]);
     __syncthreads();
     if (i < n) order[base[b] + rank] = (uint32_t)i;
+}
+// The order for n >= 128 messages with offsets d_off, built on `st` in the stream's scratch (slot 11): *ord = n x uint32 on the
+// device.  Smaller batches (*ord = nullptr) run in index order.  Shared by the hash batches and the bash-prg batches.
+err_t ragged_launch_order(const uint64_t *off, size_t n, hipStream_t st, const uint32_t **ord)
+{
+    *ord = nullptr;
+    if (n < 128) return ERR_OK;
+    void *scr = nullptr;
+    err_t code = scratch_for_stream(st, 11, 128 * 4 + n * 4, &scr);
+    if (code != ERR_OK) return code;
+    unsigned *work = (unsigned *)scr;
+    uint32_t *order = (uint32_t *)(work + 128);
+    B2H_TRY(hipMemsetAsync(work, 0, 128 * 4, st));
+    const dim3 gn((unsigned)((n + 255) / 256)), tn(256);
+    hipLaunchKernelGGL(ragged_hist_kernel, gn, tn, 0, st, off, n, work);
+    hipLaunchKernelGGL(ragged_scatter_kernel, gn, tn, 0, st, off, n, work, order);
+    *ord = order;
+    return ERR_OK;
 }
 
 constexpr uint64_t RAGGED_LONG = 4096;     // bytes; see bench.py --only ragged and DESIGN.md 4.7
@@ -843,18 +867,9 @@ err_t launch_hash_ragged(size_t alg, const void *d_data, const void *d_off, cons
     const dim3 g((unsigned)((n + 63) / 64)), t(64);
     const uint8_t *data = (const uint8_t *)d_data;
     const uint64_t *off = (const uint64_t *)d_off;
-    if (!ord && n >= 128) {                          // no order given: bucket the lengths on the device
-        void *scr = nullptr;
-        err_t code = scratch_for_stream(st, 11, 192 * 4 + n * 4, &scr);
+    if (!ord) {                                      // no order given: bucket the lengths on the device
+        const err_t code = ragged_launch_order(off, n, st, &ord);
         if (code != ERR_OK) return code;
-        unsigned *work = (unsigned *)scr;
-        uint32_t *order = (uint32_t *)(work + 192);
-        B2H_TRY(hipMemsetAsync(work, 0, 192 * 4, st));
-        const dim3 gn((unsigned)((n + 255) / 256)), tn(256);
-        hipLaunchKernelGGL(ragged_hist_kernel, gn, tn, 0, st, off, n, work);
-        hipLaunchKernelGGL(ragged_scan_kernel, dim3(1), dim3(64), 0, st, work);
-        hipLaunchKernelGGL(ragged_scatter_kernel, gn, tn, 0, st, off, n, work, order);
-        ord = order;
     }
     uint8_t *dig = (uint8_t *)d_digests;
     // bash: messages of >= RAGGED_LONG bytes go to the 8-lanes-per-message kernel (a 4x shorter serial chain),

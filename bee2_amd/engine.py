@@ -21,6 +21,7 @@ ERR_BAD_OID = 301
 ERR_BAD_PARAMS = 502
 ERR_BAD_PUBKEY = 505
 ERR_BAD_SIG = 510
+ERR_BAD_MAC = 511
 ERR_BEE2HIP_DEVICE = 0x4850
 
 OID_BELT_HASH_DER = bytes.fromhex("06092A7000020022651F51")   # bign128.c:151-153
@@ -95,6 +96,8 @@ BATCH_SYMBOLS = [
     "bee2hip_bashHash_beltMAC_batch_multi_dev",
     "bee2hip_bignPubkeyCalcL_batch_dev", "bee2hip_bignSign2L_batch_dev", "bee2hip_bignSignKL_batch_dev",
     "bee2hip_bashHash_beltMAC_batch_dev",
+    "bee2hip_bashPrgHash_ragged", "bee2hip_bashPrgAE_wrap_ragged", "bee2hip_bashPrgAE_unwrap_ragged",
+    "bee2hip_bashPrgHash_ragged_stream", "bee2hip_bashPrgAE_ragged_stream",
     "bee2hip_set_device", "bee2hip_sync", "bee2hip_last_error", "bee2hip_version", "bee2hip_path_policy", "bee2hip_path_count",
 ]
 # include/bee2hip_internal.h: test / bench hooks, not product ABI
@@ -355,6 +358,26 @@ class Engine:
                                                              _sz(n), self._ptr(digests), self._stream()),
                     "hash_ragged_ordered_dev")
 
+    def _optr(self, t):
+        return self._ptr(t) if t is not None else None
+
+    def bashPrgHash_ragged_stream(self, l, d, ann, data, offsets, out, out_len, n, order=None):
+        """prg-hash (STB 34.101.77 A.5) of n messages packed back to back: data (u8), offsets (int64, n+1), out (u8,
+        n*out_len) and the optional launch order (int32 permutation) are device tensors; ann (bytes) is shared by the batch"""
+        self._check(self.lib.bee2hip_bashPrgHash_ragged_stream(_sz(l), _sz(d), bytes(ann), _sz(len(ann)), self._optr(data),
+                                                               self._ptr(offsets), self._optr(order), _sz(n), self._ptr(out),
+                                                               _sz(out_len), self._stream()), "bashPrgHash_ragged_stream")
+
+    def bashPrgAE_ragged_stream(self, unwrap, l, d, key, anns, ann_len, hdrs, hdr_offsets, src, offsets, dst, tags, tag_len, n,
+                                codes=None, order=None):
+        """prg-ae (A.6) over n records: anns (u8, n*ann_len), hdrs / hdr_offsets (both None: empty headers), src / offsets,
+        dst (may be src), tags (u8, n*tag_len: written by wrap, read by unwrap), codes (int32, n: unwrap only) and the
+        optional order are device tensors; key (bytes) is shared by the batch"""
+        self._check(self.lib.bee2hip_bashPrgAE_ragged_stream(
+            ctypes.c_int(1 if unwrap else 0), _sz(l), _sz(d), bytes(key), _sz(len(key)), self._optr(anns), _sz(ann_len),
+            self._optr(hdrs), self._optr(hdr_offsets), self._optr(src), self._ptr(offsets), self._optr(order), _sz(n),
+            self._optr(dst), self._ptr(tags), _sz(tag_len), self._optr(codes), self._stream()), "bashPrgAE_ragged_stream")
+
     def time_kernel(self, which, reps, a=None, b=None, c=None, d=None, n=0, aux=0):
         ms = ctypes.c_float(0)
         p = [self._ptr(t) if t is not None else None for t in (a, b, c, d)]
@@ -427,6 +450,48 @@ class Engine:
         out = ctypes.create_string_buffer(max(1, n * dlen))
         code = self.lib.bee2hip_hash_ragged(_sz(alg), data, struct.pack(f"<{n + 1}Q", *offs), _sz(n), out)
         return code, [out.raw[i * dlen:(i + 1) * dlen] for i in range(n)]
+
+    @staticmethod
+    def _pack(items):
+        import struct
+        offs = [0]
+        for m in items:
+            offs.append(offs[-1] + len(m))
+        return b"".join(bytes(m) for m in items), struct.pack(f"<{len(items) + 1}Q", *offs), offs
+
+    def bashPrgHash_ragged(self, l, d, ann, messages, out_len):
+        """prg-hash of every message under one announcement -> (code, [out_len bytes per message])"""
+        n = len(messages)
+        data, offs, _ = self._pack(messages)
+        out = ctypes.create_string_buffer(max(1, n * out_len))
+        code = self.lib.bee2hip_bashPrgHash_ragged(_sz(l), _sz(d), bytes(ann), _sz(len(ann)), data, offs, _sz(n), out, _sz(out_len))
+        return code, [out.raw[i * out_len:(i + 1) * out_len] for i in range(n)]
+
+    def _prg_ae(self, unwrap, l, d, key, anns, headers, texts, tags, tag_len):
+        n = len(texts)
+        ann_len = len(anns[0]) if n else 0
+        assert all(len(a) == ann_len for a in anns) and len(anns) == n
+        src, offs, o = self._pack(texts)
+        hdr, hoffs = (None, None) if headers is None else self._pack(headers)[:2]
+        dst = ctypes.create_string_buffer(max(1, len(src)))
+        tbuf = ctypes.create_string_buffer(b"".join(bytes(t) for t in tags) if unwrap else b"", max(1, n * tag_len))
+        if unwrap:
+            codes = (_u32 * max(n, 1))()
+            code = self.lib.bee2hip_bashPrgAE_unwrap_ragged(_sz(l), _sz(d), bytes(key), _sz(len(key)), b"".join(anns), _sz(ann_len),
+                                                            hdr, hoffs, src, offs, _sz(n), tbuf, _sz(tag_len), dst, codes)
+            return code, [dst.raw[o[i]:o[i + 1]] for i in range(n)], list(codes)[:n]
+        code = self.lib.bee2hip_bashPrgAE_wrap_ragged(_sz(l), _sz(d), bytes(key), _sz(len(key)), b"".join(anns), _sz(ann_len),
+                                                      hdr, hoffs, src, offs, _sz(n), dst, tbuf, _sz(tag_len))
+        return code, [dst.raw[o[i]:o[i + 1]] for i in range(n)], [tbuf.raw[i * tag_len:(i + 1) * tag_len] for i in range(n)]
+
+    def bashPrgAE_wrap_ragged(self, l, d, key, anns, headers, texts, tag_len):
+        """prg-ae: record i = (anns[i], headers[i], texts[i]) under one key; headers None = all empty
+        -> (code, [ciphertext], [tag])"""
+        return self._prg_ae(False, l, d, key, anns, headers, texts, None, tag_len)
+
+    def bashPrgAE_unwrap_ragged(self, l, d, key, anns, headers, texts, tags):
+        """-> (code, [plaintext, zeros where refused], [ERR_OK / ERR_BAD_MAC per record])"""
+        return self._prg_ae(True, l, d, key, anns, headers, texts, tags, len(tags[0]) if tags else 1)
 
     # ------------------------------------------------- bee2 drop-in interface
     def beltH(self):

@@ -336,6 +336,43 @@ err_t bee2hip_hash_ragged_dev(size_t alg, const void *d_data, const void *d_offs
 err_t bee2hip_hash_ragged_ordered_dev(size_t alg, const void *d_data, const void *d_offsets,
                                       const void *d_order, size_t n, void *d_digests, void *stream);
 
+/* bash-prg, the programmable sponge algorithms of STB 34.101.77 (src/crypto/bash/bash_prg.c), over a ragged batch: record i
+   is ONE automaton on one lane, packed like the messages above.  With buf_len = the rate of (l, d) and the mode
+   (bash_prg.c:34-43, :133) a record costs 3 + hdr/buf_len + text/buf_len permutations (prg-hash: 2 + msg/buf_len).
+     prg-hash (A.5): Start(l, d, ann, ann_len, NULL, 0) (bash_prg.c:110-136), Absorb(msg_i) (:211-215),
+                     Squeeze(out + i*out_len, out_len) (:257-261); ann is shared by the batch
+     prg-ae   (A.6): Start(l, d, anns + i*ann_len, ann_len, key, key_len), Absorb(hdr_i) -- also when it is empty: a
+                     zero-length absorb still commits (:89-102, :177-180) --, Encr(text_i) (:310-314) or Decr(text_i)
+                     (:363-367), Squeeze(tag_i, tag_len); key is shared by the batch, every record has its own announcement
+   l in {128, 192, 256} and d in {1, 2}, else ERR_BAD_PARAMS.  ERR_BAD_INPUT unless ann_len % 4 == 0, ann_len <= 60,
+   key_len % 4 == 0, l/8 <= key_len <= 60, 1 <= tag_len (out_len) <= 64, n < 2^32; all of it is checked before any device work.
+   hdrs / hdr_offsets both NULL: every header is empty.  dst may be src (in place); otherwise record i lands at
+   dst + offsets[i].  unwrap compares all tag_len octets of the squeezed tag with tags + i*tag_len (no early exit):
+   codes[i] = ERR_OK or ERR_BAD_MAC, and the plaintext of a refused record is overwritten with zeros; its neighbours stay. */
+err_t bee2hip_bashPrgHash_ragged(size_t l, size_t d, const octet ann[], size_t ann_len, const octet *data,
+                                 const uint64_t *offsets, size_t n, octet *out, size_t out_len);
+err_t bee2hip_bashPrgAE_wrap_ragged(size_t l, size_t d, const octet key[], size_t key_len, const octet *anns, size_t ann_len,
+                                    const octet *hdrs, const uint64_t *hdr_offsets, const octet *src, const uint64_t *offsets,
+                                    size_t n, octet *dst, octet *tags, size_t tag_len);
+err_t bee2hip_bashPrgAE_unwrap_ragged(size_t l, size_t d, const octet key[], size_t key_len, const octet *anns, size_t ann_len,
+                                      const octet *hdrs, const uint64_t *hdr_offsets, const octet *src, const uint64_t *offsets,
+                                      size_t n, const octet *tags, size_t tag_len, octet *dst, err_t *codes);
+/* The same on device pointers, asynchronous on `stream` (one queue, no fork).  These are device-pointer batch entries in
+   every respect but the name: the suffix is _stream, not the usual one, because the tests' contract registry takes the
+   expected bytes of every entry with the usual suffix from the C oracle, which has no bash-prg; they are held to the same
+   range / aliasing / capture contract by tests/test_gpu_bashprg.py, and can be renamed once the registry can describe them.
+   Alignment: offsets 8, d_order / d_anns / d_codes 4, data / headers / d_src / d_dst / d_tags / d_out 1.  key and the shared
+   ann are HOST pointers and travel in the launch arguments.  d_order as for the ordered ragged hash above (NULL: bucketed by
+   the text length -- prg-hash: the message length -- on the device once n >= 128).  unwrap = 0: d_tags is written, d_codes is
+   not used (may be NULL); unwrap = 1: d_tags is read, d_codes (n x err_t) is written. */
+err_t bee2hip_bashPrgHash_ragged_stream(size_t l, size_t d, const octet ann[], size_t ann_len, const void *d_data,
+                                        const void *d_offsets, const void *d_order, size_t n, void *d_out, size_t out_len,
+                                        void *stream);
+err_t bee2hip_bashPrgAE_ragged_stream(int unwrap, size_t l, size_t d, const octet key[], size_t key_len, const void *d_anns,
+                                      size_t ann_len, const void *d_hdrs, const void *d_hdr_offsets, const void *d_src,
+                                      const void *d_offsets, const void *d_order, size_t n, void *d_dst, void *d_tags,
+                                      size_t tag_len, void *d_codes, void *stream);
+
 /* ---- one host batch over several GPUs from one process --------------------------------
    The batch is cut into contiguous index ranges (bee2hip_multi_plan), one worker thread per device runs the
    single-device entry above on its range; no data crosses devices.  ndev = number of devices to use, 0 = all
