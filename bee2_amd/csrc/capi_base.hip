@@ -46,35 +46,32 @@ extern "C" err_t bee2hip_bashF_batch(octet *states, size_t n)
 try {
     if (n == 0) return ERR_OK;
     if (!states) return ERR_BAD_INPUT;
-    Scratch &s = t_scr[0];
-    err_t code = s.need(n * 192);
-    if (code != ERR_OK) return code;
+    Stage sg(0, false, "bee2hip_bashF_batch staging");
+    const size_t o = sg.add(n * 192);
+    B2H_OK(sg.open());
     if (n * 192 >= DUPLEX_MIN)              // chunks of 2^16 states = 12 MiB: upload, permute and download overlap
-        return duplex_inplace(states, (octet *)s.p, 192, n, (size_t)1 << DUPLEX_LOG2_STATES,
+        return duplex_inplace(states, sg.at(o), 192, n, (size_t)1 << DUPLEX_LOG2_STATES,
                               [](octet *d, size_t, size_t cnt, hipStream_t st) { return launch_bashF_batch(d, cnt, st); });
-    B2H_TRY(h2d(s.p, states, n * 192));
-    code = launch_bashF_batch(s.p, n, nullptr);
-    if (code != ERR_OK) return code;
-    B2H_TRY(d2h(states, s.p, n * 192));
-    return ERR_OK;
+    B2H_OK(sg.in(o, states, n * 192));
+    B2H_OK(launch_bashF_batch(sg.at(o), n, nullptr));
+    return sg.out(states, o, n * 192);
 } B2H_CATCH
 
 // E_K over host blocks (n small): the only way the drop-in layer evaluates belt
 static err_t encr_host_blocks(uint32_t *blocks, size_t n, const u32 key[8])
 {
     return with_host(K_PRIM, n * 16, "belt block encryption", [&]() -> err_t {
-        err_t code = ensure_device();
-        if (code != ERR_OK) return code;
-        Scratch &s = t_scr[1];
-        code = s.need(n * 16);
-        if (code != ERR_OK) return code;
-        B2H_TRY(h2d(s.p, blocks, n * 16));
-        code = launch_belt_encr_blocks(s.p, n, key, nullptr);
-        if (code != ERR_OK) return code;
-        B2H_TRY(d2h(blocks, s.p, n * 16));
-        return ERR_OK;
+        Stage sg(1, false, "belt block encryption staging");
+        const size_t o = sg.add(n * 16);
+        B2H_OK(sg.open());
+        B2H_OK(sg.in(o, blocks, n * 16));
+        B2H_OK(launch_belt_encr_blocks(sg.at(o), n, key, nullptr));
+        return sg.out(blocks, o, n * 16);
     }, [&] { for (size_t i = 0; i < n; ++i) hostp::belt_encr(hostT(), blocks + 4 * i, key); });
 }
+
+// the belt key lengths (belt.h)
+static inline bool key_len_ok(size_t len) { return len == 16 || len == 24 || len == 32; }
 
 // a device failure inside a void bee2 function cannot be reported through the bee2
 // signature: fail loudly instead of returning wrong bytes.

@@ -26,28 +26,24 @@ try {
 // run the device sponge over `count` host bytes for one state
 static err_t sponge_gpu(bash_hash_st *st, const octet *buf, size_t count)
 {
-    Scratch &s = t_scr[0];
-    err_t code = s.need(sizeof(bash_hash_st) + count + 16, true);
-    if (code != ERR_OK) return code;
-    octet *d = (octet *)s.p;
-    B2H_TRY(h2d(d, st, sizeof *st));
-    B2H_TRY(h2d(d + sizeof *st, buf, count));
-    const octet *dd = d + sizeof *st;
+    Stage sg(0, true, "bashHashStepH staging");
+    const size_t o_st = sg.add(sizeof *st), o_in = sg.add(count);
+    B2H_OK(sg.open(16));
+    B2H_OK(sg.in(o_st, st, sizeof *st));
+    B2H_OK(sg.in(o_in, buf, count));
+    octet *d = sg.at(o_st);
+    const octet *dd = sg.at(o_in);
     // large chunk: byte-wise up to the next block boundary, whole rate blocks with 8 lanes (a 3x shorter chain,
     // DESIGN.md 4.7), the remainder byte-wise again
     const size_t head = st->pos ? st->buf_len - st->pos : 0;
     if (count >= 4096 + head) {
         const size_t blocks = (count - head) / st->buf_len, tail = count - head - blocks * st->buf_len;
-        if (head) { code = launch_bash_sponge(d, dd, 0, head, 1, 0, nullptr); if (code != ERR_OK) return code; }
-        code = launch_bash_sponge_cols(d, dd + head, blocks, nullptr);
-        if (code != ERR_OK) return code;
-        if (tail) { code = launch_bash_sponge(d, dd + head + blocks * st->buf_len, 0, tail, 1, 0, nullptr); if (code != ERR_OK) return code; }
-    } else {
-        code = launch_bash_sponge(d, dd, 0, count, 1, 0, nullptr);
-        if (code != ERR_OK) return code;
-    }
-    B2H_TRY(d2h(st, d, sizeof *st));
-    return ERR_OK;
+        if (head) B2H_OK(launch_bash_sponge(d, dd, 0, head, 1, 0, nullptr));
+        B2H_OK(launch_bash_sponge_cols(d, dd + head, blocks, nullptr));
+        if (tail) B2H_OK(launch_bash_sponge(d, dd + head + blocks * st->buf_len, 0, tail, 1, 0, nullptr));
+    } else
+        B2H_OK(launch_bash_sponge(d, dd, 0, count, 1, 0, nullptr));
+    return sg.out(st, o_st, sizeof *st);
 }
 
 static err_t sponge_host(bash_hash_st *st, const octet *buf, size_t count)

@@ -93,14 +93,12 @@ static err_t ctr_bulk(void *buf_, size_t count, void *ctr_state, bool allow_host
             // block and the gamma the state keeps -- takes the plain path below, from the advanced counter
             const size_t CH = (size_t)1 << DUPLEX_LOG2_BLOCKS;             // blocks per chunk (2^20 = 16 MiB)
             const size_t pipe_blocks = (count - 1) / (16 * CH) * CH;
-            err_t pc = ensure_device();
-            if (pc != ERR_OK) return pc;
-            Scratch &ps = t_scr[2];
-            pc = ps.need(pipe_blocks * 16);
-            if (pc != ERR_OK) return pc;
+            Stage ps(2, false, "beltCTR staging");
+            const size_t o = ps.add(pipe_blocks * 16);
+            B2H_OK(ps.open());
             const u32 *key = st->key, *ctr = st->ctr;
             size_t done = 0;
-            pc = duplex_inplace(buf, (octet *)ps.p, 16, pipe_blocks, CH, [key, ctr](octet *d, size_t first, size_t cnt, hipStream_t s2) {
+            const err_t pc = duplex_inplace(buf, ps.at(o), 16, pipe_blocks, CH, [key, ctr](octet *d, size_t first, size_t cnt, hipStream_t s2) {
                 return launch_belt_ctr_blocks(d, cnt, key, ctr, first, nullptr, s2);
             }, &done);
             // the blocks that came back ARE encrypted in the caller's buffer, also when a later chunk failed: whoever goes on
@@ -112,20 +110,16 @@ static err_t ctr_bulk(void *buf_, size_t count, void *ctr_state, bool allow_host
         }
         const size_t full = count / 16, tail = count % 16;
         const size_t nblk = full + (tail ? 1 : 0);
-        err_t code = ensure_device();
-        if (code != ERR_OK) return code;
-        Scratch &s = t_scr[2];
-        code = s.need(nblk * 16 + 16);
-        if (code != ERR_OK) return code;
-        octet *d = (octet *)s.p;
-        if (tail) B2H_TRY(zero_staging(d + full * 16, 16));
-        B2H_TRY(h2d(d, buf, count));
+        Stage sg(2, false, "beltCTR staging");
+        const size_t o = sg.add(nblk * 16), o_g = sg.add(16);        // the blocks, the gamma of the last one behind them
+        B2H_OK(sg.open());
+        if (tail) B2H_TRY(zero_staging(sg.at(o + full * 16), 16));
+        B2H_OK(sg.in(o, buf, count));
         // first_block = 0: the offset is relative to the state's *current* counter
-        code = launch_belt_ctr_blocks(d, nblk, st->key, st->ctr, 0, d + nblk * 16, nullptr);
-        if (code != ERR_OK) return code;
+        B2H_OK(launch_belt_ctr_blocks(sg.at(o), nblk, st->key, st->ctr, 0, sg.at(o_g), nullptr));
         octet last[16];
-        B2H_TRY(d2h(last, d + nblk * 16, 16));
-        B2H_TRY(d2h(buf, d, count));
+        B2H_OK(sg.out(last, o_g, 16));
+        B2H_OK(sg.out(buf, o, count));
         memcpy(st->block, last, 16);
         ctr_add(st->ctr, nblk);                        // what nblk beltBlockIncU32 calls leave
         st->reserved = tail ? 16 - tail : 0;
@@ -145,7 +139,7 @@ try {
 extern "C" err_t beltCTR(void *dest, const void *src, size_t count, const octet key[], size_t len,
                          const octet iv[16])
 try {
-    if ((len != 16 && len != 24 && len != 32) || (count && (!src || !dest)) || !key || !iv)
+    if (!key_len_ok(len) || (count && (!src || !dest)) || !key || !iv)
         return ERR_BAD_INPUT;
     belt_ctr_st st[1];                                // (72 bytes: no blob, nothing to free on any path)
     beltCTRStart(st, key, len, iv);
@@ -162,19 +156,13 @@ extern "C" size_t beltMAC_keep(void) { return sizeof(belt_mac_st); }
 static err_t mac_host(belt_mac_st *st, const octet *buf, size_t count, int mode)
 {
     return with_host(K_SERIAL, count, "beltMAC", [&]() -> err_t {
-        err_t code = ensure_device();
-        if (code != ERR_OK) return code;
-        Scratch &s = t_scr[1];
-        code = s.need(sizeof(belt_mac_st) + 8 + count + 16);
-        if (code != ERR_OK) return code;
-        octet *d = (octet *)s.p;
-        const size_t off = (sizeof(belt_mac_st) + 15) & ~(size_t)15;
-        B2H_TRY(h2d(d, st, sizeof *st));
-        if (count) B2H_TRY(h2d(d + off, buf, count));
-        code = launch_belt_mac(d, d + off, 0, count, 1, mode, nullptr);
-        if (code != ERR_OK) return code;
-        B2H_TRY(d2h(st, d, sizeof *st));
-        return ERR_OK;
+        Stage sg(1, false, "beltMAC staging");
+        const size_t o_st = sg.add(sizeof *st), o_in = sg.add(count);
+        B2H_OK(sg.open(16));
+        B2H_OK(sg.in(o_st, st, sizeof *st));
+        B2H_OK(sg.in(o_in, buf, count));
+        B2H_OK(launch_belt_mac(sg.at(o_st), sg.at(o_in), 0, count, 1, mode, nullptr));
+        return sg.out(st, o_st, sizeof *st);
     }, [&] { hostp::mac_step(hostT(), st->key, st->s, st->r, st->mac, st->block, &st->filled, buf, count, mode); });
 }
 
@@ -218,7 +206,7 @@ extern "C" bool_t beltMACStepV(const octet mac[8], void *state) try { return bel
 
 extern "C" err_t beltMAC(octet mac[8], const void *src, size_t count, const octet key[], size_t len)
 try {
-    if ((len != 16 && len != 24 && len != 32) || (count && !src) || !key || !mac) return ERR_BAD_INPUT;
+    if (!key_len_ok(len) || (count && !src) || !key || !mac) return ERR_BAD_INPUT;
     belt_mac_st *st = new (std::nothrow) belt_mac_st;
     if (!st) return ERR_OUTOFMEMORY;
     beltMACStart(st, key, len);
@@ -233,16 +221,12 @@ try {
 static err_t decr_host_blocks(uint32_t *blocks, size_t n, const u32 key[8])
 {
     return with_host(K_PRIM, n * 16, "belt block decryption", [&]() -> err_t {
-        err_t code = ensure_device();
-        if (code != ERR_OK) return code;
-        Scratch &s = t_scr[1];
-        code = s.need(n * 16);
-        if (code != ERR_OK) return code;
-        B2H_TRY(h2d(s.p, blocks, n * 16));
-        code = launch_belt_decr_blocks(s.p, n, key, nullptr);
-        if (code != ERR_OK) return code;
-        B2H_TRY(d2h(blocks, s.p, n * 16));
-        return ERR_OK;
+        Stage sg(1, false, "belt block decryption staging");
+        const size_t o = sg.add(n * 16);
+        B2H_OK(sg.open());
+        B2H_OK(sg.in(o, blocks, n * 16));
+        B2H_OK(launch_belt_decr_blocks(sg.at(o), n, key, nullptr));
+        return sg.out(blocks, o, n * 16);
     }, [&] { for (size_t i = 0; i < n; ++i) hostp::belt_decr(hostT(), blocks + 4 * i, key); });
 }
 
@@ -294,17 +278,12 @@ static err_t modes_host(int mode, octet *buf, size_t nblocks, const u32 key[8], 
     u32 iv[4] = {0, 0, 0, 0};
     if (chain) for (int i = 0; i < 4; ++i) iv[i] = load32le(chain + 4 * i);
     return with_host(K_PARALLEL, bytes, "belt ECB / CBC blocks", [&]() -> err_t {
-        err_t code = ensure_device();
-        if (code != ERR_OK) return code;
-        Scratch &s = t_scr[2];
-        code = s.need(2 * bytes);
-        if (code != ERR_OK) return code;
-        octet *d = (octet *)s.p;
-        B2H_TRY(h2d(d, buf, bytes));
-        code = launch_belt_modes(mode, d, d + bytes, nblocks, key, iv, nullptr);
-        if (code != ERR_OK) return code;
-        B2H_TRY(d2h(buf, d + bytes, bytes));
-        return ERR_OK;
+        Stage sg(2, false, "belt ECB / CBC staging");
+        const size_t o_src = sg.add(bytes), o_dst = sg.add(bytes);
+        B2H_OK(sg.open());
+        B2H_OK(sg.in(o_src, buf, bytes));
+        B2H_OK(launch_belt_modes(mode, sg.at(o_src), sg.at(o_dst), nblocks, key, iv, nullptr));
+        return sg.out(buf, o_dst, bytes);
     }, [&] { hostp::modes_blocks(hostT(), mode, buf, nblocks, key, iv); });
 }
 
@@ -338,7 +317,7 @@ extern "C" void beltECBStepD(void *buf, size_t count, void *state) try { ecb_ste
 
 static err_t ecb_oneshot(void *dest, const void *src, size_t count, const octet key[], size_t len, int decr)
 {
-    if (count < 16 || (len != 16 && len != 24 && len != 32) || !src || !dest || !key) return ERR_BAD_INPUT;
+    if (count < 16 || !key_len_ok(len) || !src || !dest || !key) return ERR_BAD_INPUT;
     belt_ecb_st st;
     beltECBStart(&st, key, len);
     memmove(dest, src, count);
@@ -391,18 +370,13 @@ try {
 static err_t dwp_absorb_host(u32 t_out[4], const u32 t[4], const u32 r[4], const octet *data, size_t nbytes)
 {
     return with_host(K_POLY, nbytes, "belt-dwp authentication", [&]() -> err_t {
-        err_t code = ensure_device();
-        if (code != ERR_OK) return code;
-        Scratch &sc = t_scr[2];
-        const size_t off = (nbytes + 15) & ~(size_t)15;
-        code = sc.need(off + 16);
-        if (code != ERR_OK) return code;
-        octet *d = (octet *)sc.p;
-        if (nbytes) B2H_TRY(h2d(d, data, nbytes));
-        code = launch_belt_polyhash(d, nbytes, r, t, d + off, nullptr);
-        if (code != ERR_OK) return code;
+        Stage sg(2, false, "belt-dwp authentication staging");
+        const size_t o_in = sg.add(nbytes), o_t = sg.add(16);
+        B2H_OK(sg.open());
+        B2H_OK(sg.in(o_in, data, nbytes));
+        B2H_OK(launch_belt_polyhash(sg.at(o_in), nbytes, r, t, sg.at(o_t), nullptr));
         octet out[16];
-        B2H_TRY(d2h(out, d + off, 16));
+        B2H_OK(sg.out(out, o_t, 16));
         for (int i = 0; i < 4; ++i) t_out[i] = load32le(out + 4 * i);
         return ERR_OK;
     }, [&] {
@@ -470,7 +444,7 @@ try {
 extern "C" err_t beltDWPWrap(void *dest, octet mac[8], const void *src1, size_t count1, const void *src2,
                              size_t count2, const octet key[], size_t len, const octet iv[16])
 try {
-    if ((len != 16 && len != 24 && len != 32) || (count1 && (!src1 || !dest)) || (count2 && !src2) || !key || !iv || !mac)
+    if (!key_len_ok(len) || (count1 && (!src1 || !dest)) || (count2 && !src2) || !key || !iv || !mac)
         return ERR_BAD_INPUT;
     belt_dwp_st st;
     beltDWPStart(&st, key, len, iv);
@@ -484,7 +458,7 @@ try {
 extern "C" err_t beltDWPUnwrap(void *dest, const void *src1, size_t count1, const void *src2, size_t count2,
                                const octet mac[8], const octet key[], size_t len, const octet iv[16])
 try {
-    if ((len != 16 && len != 24 && len != 32) || (count1 && (!src1 || !dest)) || (count2 && !src2) || !key || !iv || !mac)
+    if (!key_len_ok(len) || (count1 && (!src1 || !dest)) || (count2 && !src2) || !key || !iv || !mac)
         return ERR_BAD_INPUT;
     belt_dwp_st st;
     beltDWPStart(&st, key, len, iv);
@@ -517,19 +491,13 @@ try {
 static err_t hash_stream_host(u32 hs[12], const octet *data, size_t nblocks, int fin, uint64_t lo, uint64_t hi)
 {
     return with_host(K_SERIAL, nblocks * 32, "beltHash", [&]() -> err_t {
-        err_t code = ensure_device();
-        if (code != ERR_OK) return code;
-        Scratch &sc = t_scr[2];
-        const size_t bytes = nblocks * 32;
-        code = sc.need(bytes + 64, true);
-        if (code != ERR_OK) return code;
-        octet *d = (octet *)sc.p;
-        if (bytes) B2H_TRY(h2d(d, data, bytes));
-        B2H_TRY(h2d(d + bytes, hs, 48));
-        code = launch_belt_hash_stream(d + bytes, d, nblocks, fin, lo, hi, nullptr);
-        if (code != ERR_OK) return code;
-        B2H_TRY(d2h(hs, d + bytes, 48));
-        return ERR_OK;
+        Stage sg(2, true, "beltHash staging");
+        const size_t o_in = sg.add(nblocks * 32), o_hs = sg.add(48);
+        B2H_OK(sg.open(16));
+        B2H_OK(sg.in(o_in, data, nblocks * 32));
+        B2H_OK(sg.in(o_hs, hs, 48));
+        B2H_OK(launch_belt_hash_stream(sg.at(o_hs), sg.at(o_in), nblocks, fin, lo, hi, nullptr));
+        return sg.out(hs, o_hs, 48);
     }, [&] { hostp::hash_stream(hostT(), hs, data, nblocks, fin, lo, hi); });
 }
 extern "C" void beltHashStepH(const void *buf, size_t count, void *state)
@@ -622,18 +590,13 @@ try {
 static err_t sde_host(int decr, octet *buf, size_t count, const octet iv[16], belt_sde_st *st)
 {
     const err_t rc = with_host(K_SERIAL, count, "beltSDE", [&]() -> err_t {
-        err_t code = ensure_device();
-        if (code != ERR_OK) return code;
-        Scratch &sc = t_scr[2];
-        code = sc.need(count + 16);
-        if (code != ERR_OK) return code;
-        octet *d = (octet *)sc.p;
-        B2H_TRY(h2d(d, buf, count));
-        B2H_TRY(h2d(d + count, iv, 16));
-        code = launch_belt_sde(decr, d, count / 16, 1, st->wbl->key, d + count, nullptr);
-        if (code != ERR_OK) return code;
-        B2H_TRY(d2h(buf, d, count));
-        return ERR_OK;
+        Stage sg(2, false, "beltSDE staging");
+        const size_t o = sg.add(count), o_iv = sg.add(16);
+        B2H_OK(sg.open());
+        B2H_OK(sg.in(o, buf, count));
+        B2H_OK(sg.in(o_iv, iv, 16));
+        B2H_OK(launch_belt_sde(decr, sg.at(o), count / 16, 1, st->wbl->key, sg.at(o_iv), nullptr));
+        return sg.out(buf, o, count);
     }, [&] { hostp::sde_sector(hostT(), decr, buf, count, iv, st->wbl->key); });
     if (rc == ERR_OK) st->wbl->round = decr ? 0 : 2 * (uint64_t)(count / 16);     // where the reference's loops stop (belt_wbl.c)
     return rc;
@@ -650,7 +613,7 @@ static err_t sde_oneshot(void *dest, const void *src, size_t count, const octet 
                          const octet iv[16], int decr)
 {
     // belt_sde.c:79-86
-    if (count % 16 != 0 || count < 32 || (len != 16 && len != 24 && len != 32) || !src || !dest || !key || !iv)
+    if (count % 16 != 0 || count < 32 || !key_len_ok(len) || !src || !dest || !key || !iv)
         return ERR_BAD_INPUT;
     belt_sde_st st;
     beltSDEStart(&st, key, len);
@@ -703,18 +666,14 @@ static err_t che_blocks_host(octet *buf, size_t nblocks, belt_che_st *st)
     if (nblocks == 0) return ERR_OK;
     const size_t bytes = nblocks * 16;
     return with_host(K_PARALLEL, bytes, "beltCHEStepE", [&]() -> err_t {
-        err_t code = ensure_device();
-        if (code != ERR_OK) return code;
-        Scratch &sc = t_scr[2];
-        code = sc.need(bytes + 16);
-        if (code != ERR_OK) return code;
-        octet *d = (octet *)sc.p;
-        B2H_TRY(h2d(d, buf, bytes));
-        code = launch_belt_che(d, d, nblocks, st->mac.ctr.key, st->s, 0, d + bytes, nullptr);
-        if (code != ERR_OK) return code;
+        Stage sg(2, false, "beltCHE staging");
+        const size_t o = sg.add(bytes), o_s = sg.add(16);            // the blocks, the advanced s behind them
+        B2H_OK(sg.open());
+        B2H_OK(sg.in(o, buf, bytes));
+        B2H_OK(launch_belt_che(sg.at(o), sg.at(o), nblocks, st->mac.ctr.key, st->s, 0, sg.at(o_s), nullptr));
         octet snew[16];
-        B2H_TRY(d2h(snew, d + bytes, 16));
-        B2H_TRY(d2h(buf, d, bytes));
+        B2H_OK(sg.out(snew, o_s, 16));
+        B2H_OK(sg.out(buf, o, bytes));
         for (int i = 0; i < 4; ++i) st->s[i] = load32le(snew + 4 * i);
         return ERR_OK;
     }, [&] { hostp::che_blocks(hostT(), buf, nblocks, st->mac.ctr.key, st->s); });
@@ -755,7 +714,7 @@ try {
 extern "C" err_t beltCHEWrap(void *dest, octet mac[8], const void *src1, size_t count1, const void *src2,
                              size_t count2, const octet key[], size_t len, const octet iv[16])
 try {
-    if ((len != 16 && len != 24 && len != 32) || (count1 && (!src1 || !dest)) || (count2 && !src2) || !key || !iv || !mac)
+    if (!key_len_ok(len) || (count1 && (!src1 || !dest)) || (count2 && !src2) || !key || !iv || !mac)
         return ERR_BAD_INPUT;
     belt_che_st st;
     beltCHEStart(&st, key, len, iv);
@@ -769,7 +728,7 @@ try {
 extern "C" err_t beltCHEUnwrap(void *dest, const void *src1, size_t count1, const void *src2, size_t count2,
                                const octet mac[8], const octet key[], size_t len, const octet iv[16])
 try {
-    if ((len != 16 && len != 24 && len != 32) || (count1 && (!src1 || !dest)) || (count2 && !src2) || !key || !iv || !mac)
+    if (!key_len_ok(len) || (count1 && (!src1 || !dest)) || (count2 && !src2) || !key || !iv || !mac)
         return ERR_BAD_INPUT;
     belt_che_st st;
     beltCHEStart(&st, key, len, iv);
@@ -816,18 +775,14 @@ static err_t bde_host(int decr, octet *buf, size_t nblocks, belt_bde_st *st)
     if (nblocks == 0) return ERR_OK;
     const size_t bytes = nblocks * 16;
     const err_t rc = with_host(K_PARALLEL, bytes, "beltBDE", [&]() -> err_t {
-        err_t code = ensure_device();
-        if (code != ERR_OK) return code;
-        Scratch &sc = t_scr[2];
-        code = sc.need(bytes + 16);
-        if (code != ERR_OK) return code;
-        octet *d = (octet *)sc.p;
-        B2H_TRY(h2d(d, buf, bytes));
-        code = launch_belt_bde(decr, d, d, nblocks, st->key, st->s, 0, d + bytes, nullptr);
-        if (code != ERR_OK) return code;
+        Stage sg(2, false, "beltBDE staging");
+        const size_t o = sg.add(bytes), o_s = sg.add(16);
+        B2H_OK(sg.open());
+        B2H_OK(sg.in(o, buf, bytes));
+        B2H_OK(launch_belt_bde(decr, sg.at(o), sg.at(o), nblocks, st->key, st->s, 0, sg.at(o_s), nullptr));
         octet snew[16];
-        B2H_TRY(d2h(snew, d + bytes, 16));
-        B2H_TRY(d2h(buf, d, bytes));
+        B2H_OK(sg.out(snew, o_s, 16));
+        B2H_OK(sg.out(buf, o, bytes));
         for (int i = 0; i < 4; ++i) st->s[i] = load32le(snew + 4 * i);
         return ERR_OK;
     }, [&] { hostp::bde_blocks(hostT(), decr, buf, nblocks, st->key, st->s); });
@@ -851,7 +806,7 @@ static err_t bde_oneshot(void *dest, const void *src, size_t count, const octet 
                          const octet iv[16], int decr)
 {
     // belt_bde.c:93-100, 118-125
-    if (count % 16 != 0 || count < 16 || (len != 16 && len != 24 && len != 32) || !src || !dest || !key || !iv)
+    if (count % 16 != 0 || count < 16 || !key_len_ok(len) || !src || !dest || !key || !iv)
         return ERR_BAD_INPUT;
     belt_bde_st st;
     beltBDEStart(&st, key, len, iv);
@@ -890,19 +845,15 @@ try {
     if (full) {
         // the serial chain runs on one lane of the per-message kernel (n = 1), or on the host
         die_on(with_host(K_SERIAL, full * 16, "beltCBCStepE", [&]() -> err_t {
-            err_t code = ensure_device();
-            if (code != ERR_OK) return code;
-            Scratch &s = t_scr[2];
-            code = s.need(full * 16 + 16);
-            if (code != ERR_OK) return code;
-            octet *d = (octet *)s.p;
-            B2H_TRY(h2d(d, buf, full * 16));
-            B2H_TRY(h2d(d + full * 16, st->block, 16));
-            code = launch_belt_cbc_encr(d, full, 1, st->key, d + full * 16, nullptr);
-            if (code != ERR_OK) return code;
+            Stage sg(2, false, "beltCBCStepE staging");
+            const size_t o = sg.add(full * 16), o_iv = sg.add(16);
+            B2H_OK(sg.open());
+            B2H_OK(sg.in(o, buf, full * 16));
+            B2H_OK(sg.in(o_iv, st->block, 16));
+            B2H_OK(launch_belt_cbc_encr(sg.at(o), full, 1, st->key, sg.at(o_iv), nullptr));
             octet chain[16];
-            B2H_TRY(d2h(chain, d + full * 16, 16));
-            B2H_TRY(d2h(buf, d, full * 16));
+            B2H_OK(sg.out(chain, o_iv, 16));
+            B2H_OK(sg.out(buf, o, full * 16));
             memcpy(st->block, chain, 16);
             return ERR_OK;
         }, [&] { hostp::cbc_encr_blocks(hostT(), buf, full, st->key, st->block); }), "beltCBCStepE");
@@ -946,7 +897,7 @@ try {
 static err_t cbc_oneshot(void *dest, const void *src, size_t count, const octet key[], size_t len,
                          const octet iv[16], int decr)
 {
-    if (count < 16 || (len != 16 && len != 24 && len != 32) || !src || !dest || !key || !iv) return ERR_BAD_INPUT;
+    if (count < 16 || !key_len_ok(len) || !src || !dest || !key || !iv) return ERR_BAD_INPUT;
     belt_cbc_st st;
     beltCBCStart(&st, key, len, iv);
     memmove(dest, src, count);

@@ -167,15 +167,12 @@ try {
     if (n && (!hashes || !sigs || !pubkeys || !codes)) return ERR_BAD_INPUT;
     if (!oid_der_valid(oid_der, oid_len)) return ERR_BAD_OID;
     if (n == 0) return ERR_OK;
-    code = ensure_device();
-    if (code != ERR_OK) return code;
     const size_t no = params->l / 4;                 // octets per field element
     const size_t hb = no * n, sb = (no + no / 2) * n, pb = 2 * no * n;
-    const size_t so = (hb + 15) & ~(size_t)15, po = (so + sb + 15) & ~(size_t)15, co = (po + pb + 15) & ~(size_t)15;
-    Scratch &s = t_scr[3];
-    code = s.need(co + n * 4);
-    if (code != ERR_OK) return code;
-    octet *d = (octet *)s.p;
+    Stage stage(3, false, "bee2hip_bignVerify_batch staging");
+    const size_t ho = stage.add(hb), so = stage.add(sb), po = stage.add(pb), co = stage.add(n * 4);
+    B2H_OK(stage.open());
+    octet *d = stage.at(ho);
     if (standard && n >= VERIFY_PIPE_MIN && g_verify_pipe) {
         // big host batch: chunk c + 1 is uploaded (its own stream) while the kernels of chunk c run -- the 144 n octets
         // of input are a quarter of the time of the whole call otherwise (profiles/r03_verify_hostpipe.txt)
@@ -205,14 +202,12 @@ try {
         B2H_TRY(hipMemcpy(codes, d + co, 4 * n, hipMemcpyDeviceToHost));
         return ERR_OK;
     }
-    B2H_TRY(h2d(d, hashes, hb));
-    B2H_TRY(h2d(d + so, sigs, sb));
-    B2H_TRY(h2d(d + po, pubkeys, pb));
-    code = standard ? launch_bign_verify(params->l, oid_der, oid_len, d, d + so, d + po, n, d + co, nullptr)
-                    : launch_bign_verify_generic(params, oid_der, oid_len, d, d + so, d + po, n, d + co, nullptr);
-    if (code != ERR_OK) return code;
-    B2H_TRY(d2h(codes, d + co, 4 * n));
-    return ERR_OK;
+    B2H_OK(stage.in(ho, hashes, hb));
+    B2H_OK(stage.in(so, sigs, sb));
+    B2H_OK(stage.in(po, pubkeys, pb));
+    B2H_OK(standard ? launch_bign_verify(params->l, oid_der, oid_len, d, d + so, d + po, n, d + co, nullptr)
+                    : launch_bign_verify_generic(params, oid_der, oid_len, d, d + so, d + po, n, d + co, nullptr));
+    return stage.out(codes, co, 4 * n);
 } B2H_CATCH
 
 // the three standard curves for host_bign.hpp: c, q, y_G and the fixed tables of G, built at first use
@@ -317,26 +312,18 @@ try {
     if (n == 0) return ERR_OK;
     const size_t no = params->l / 4;
     if (!standard) {                                   // general-curve kernels: the key n times through the batch entry
-        try {
-            std::vector<octet> rep(2 * no * n);
-            for (size_t i = 0; i < n; ++i) memcpy(rep.data() + 2 * no * i, pubkey, 2 * no);
-            return bee2hip_bignVerify_batch(params, oid_der, oid_len, hashes, sigs, rep.data(), n, codes);
-        } catch (const std::bad_alloc &) { return ERR_OUTOFMEMORY; }
+        std::vector<octet> rep(2 * no * n);
+        for (size_t i = 0; i < n; ++i) memcpy(rep.data() + 2 * no * i, pubkey, 2 * no);
+        return bee2hip_bignVerify_batch(params, oid_der, oid_len, hashes, sigs, rep.data(), n, codes);
     }
-    code = ensure_device();
-    if (code != ERR_OK) return code;
     const size_t hb = no * n, sb = (no + no / 2) * n;
-    const size_t so = (hb + 15) & ~(size_t)15, co = (so + sb + 15) & ~(size_t)15;
-    Scratch &s = t_scr[3];
-    code = s.need(co + n * 4);
-    if (code != ERR_OK) return code;
-    octet *d = (octet *)s.p;
-    B2H_TRY(h2d(d, hashes, hb));
-    B2H_TRY(h2d(d + so, sigs, sb));
-    code = verify_onekey_dev(params->l, oid_der, oid_len, d, d + so, pubkey, n, d + co, nullptr);
-    if (code != ERR_OK) return code;
-    B2H_TRY(d2h(codes, d + co, 4 * n));
-    return ERR_OK;
+    Stage sg(3, false, "bee2hip_bignVerify_onekey_batch staging");
+    const size_t ho = sg.add(hb), so = sg.add(sb), co = sg.add(n * 4);
+    B2H_OK(sg.open());
+    B2H_OK(sg.in(ho, hashes, hb));
+    B2H_OK(sg.in(so, sigs, sb));
+    B2H_OK(verify_onekey_dev(params->l, oid_der, oid_len, sg.at(ho), sg.at(so), pubkey, n, sg.at(co), nullptr));
+    return sg.out(codes, co, 4 * n);
 } B2H_CATCH
 
 // ---- n signatures of K signers: key_index[i] < nkeys says whose signature i is ----
@@ -371,33 +358,25 @@ try {
     if (n == 0) return ERR_OK;
     const size_t no = params->l / 4;
     if (!standard || nkeys > 4096) {                   // general-curve kernels / a crowd of signers: every signature with its key, the general entry
-        try {
-            std::vector<octet> rep(2 * no * n);
-            std::vector<size_t> bad;
-            for (size_t i = 0; i < n; ++i) {
-                if (key_index[i] >= nkeys) { bad.push_back(i); memcpy(rep.data() + 2 * no * i, pubkeys, 2 * no); }
-                else memcpy(rep.data() + 2 * no * i, pubkeys + 2 * no * key_index[i], 2 * no);
-            }
-            code = bee2hip_bignVerify_batch(params, oid_der, oid_len, hashes, sigs, rep.data(), n, codes);
-            if (code == ERR_OK) for (size_t i : bad) codes[i] = ERR_BAD_INPUT;
-            return code;
-        } catch (const std::bad_alloc &) { return ERR_OUTOFMEMORY; }
+        std::vector<octet> rep(2 * no * n);
+        std::vector<size_t> bad;
+        for (size_t i = 0; i < n; ++i) {
+            if (key_index[i] >= nkeys) { bad.push_back(i); memcpy(rep.data() + 2 * no * i, pubkeys, 2 * no); }
+            else memcpy(rep.data() + 2 * no * i, pubkeys + 2 * no * key_index[i], 2 * no);
+        }
+        code = bee2hip_bignVerify_batch(params, oid_der, oid_len, hashes, sigs, rep.data(), n, codes);
+        if (code == ERR_OK) for (size_t i : bad) codes[i] = ERR_BAD_INPUT;
+        return code;
     }
-    code = ensure_device();
-    if (code != ERR_OK) return code;
     const size_t hb = no * n, sb = (no + no / 2) * n;
-    const size_t so = (hb + 15) & ~(size_t)15, io = (so + sb + 15) & ~(size_t)15, co = (io + 4 * n + 15) & ~(size_t)15;
-    Scratch &s = t_scr[3];
-    code = s.need(co + n * 4);
-    if (code != ERR_OK) return code;
-    octet *d = (octet *)s.p;
-    B2H_TRY(h2d(d, hashes, hb));
-    B2H_TRY(h2d(d + so, sigs, sb));
-    B2H_TRY(h2d(d + io, key_index, 4 * n));
-    code = launch_bign_verify_keyed(params->l, oid_der, oid_len, d, d + so, pubkeys, nkeys, d + io, n, d + co, nullptr);
-    if (code != ERR_OK) return code;
-    B2H_TRY(d2h(codes, d + co, 4 * n));
-    return ERR_OK;
+    Stage sg(3, false, "bee2hip_bignVerify_keyed_batch staging");
+    const size_t ho = sg.add(hb), so = sg.add(sb), io = sg.add(4 * n), co = sg.add(n * 4);
+    B2H_OK(sg.open());
+    B2H_OK(sg.in(ho, hashes, hb));
+    B2H_OK(sg.in(so, sigs, sb));
+    B2H_OK(sg.in(io, key_index, 4 * n));
+    B2H_OK(launch_bign_verify_keyed(params->l, oid_der, oid_len, sg.at(ho), sg.at(so), pubkeys, nkeys, sg.at(io), n, sg.at(co), nullptr));
+    return sg.out(codes, co, 4 * n);
 } B2H_CATCH
 
 extern "C" err_t bignVerify(const bign_params *params, const octet oid_der[], size_t oid_len,
@@ -472,19 +451,13 @@ try {
     }
     if (n && (!pubkeys || !codes)) return ERR_BAD_INPUT;
     if (n == 0) return ERR_OK;
-    code = ensure_device();
-    if (code != ERR_OK) return code;
-    const size_t pb = params->l / 2 * n, co = (pb + 15) & ~(size_t)15;
-    Scratch &s = t_scr[3];
-    code = s.need(co + n * 4);
-    if (code != ERR_OK) return code;
-    octet *d = (octet *)s.p;
-    B2H_TRY(h2d(d, pubkeys, pb));
-    code = standard ? launch_bign_pubkey_val(params->l, d, n, d + co, nullptr)
-                    : launch_bign_pubkey_val_generic(params, d, n, d + co, nullptr);
-    if (code != ERR_OK) return code;
-    B2H_TRY(d2h(codes, d + co, 4 * n));
-    return ERR_OK;
+    Stage sg(3, false, "bee2hip_bignPubkeyVal_batch staging");
+    const size_t pb = params->l / 2 * n, po = sg.add(pb), co = sg.add(n * 4);
+    B2H_OK(sg.open());
+    B2H_OK(sg.in(po, pubkeys, pb));
+    B2H_OK(standard ? launch_bign_pubkey_val(params->l, sg.at(po), n, sg.at(co), nullptr)
+                    : launch_bign_pubkey_val_generic(params, sg.at(po), n, sg.at(co), nullptr));
+    return sg.out(codes, co, 4 * n);
 } B2H_CATCH
 
 extern "C" err_t bignPubkeyVal(const bign_params *params, const octet pubkey[])
@@ -522,14 +495,8 @@ extern "C" err_t bign192PubkeyVal(const octet pubkey[96]) try { return level_pub
 extern "C" err_t bign256PubkeyVal(const octet pubkey[128]) try { return level_pubkey_val(2, pubkey); } B2H_CATCH
 
 // ---- 8f-4 tail: public key from private key, key generation, signing (bign_misc.c:182-229,373-417,
-// bign_sign.c:32-245).  Secrets cross the staging buffer t_scr[3]; it is overwritten with zeros before return.
-static void wipe_dev(void *p, size_t n) { if (p && n) (void)zero_staging(p, n); }
-// staged secrets are zeroed on EVERY way out of a host entry point (early error returns, an allocation that throws)
-struct WipeGuard {
-    void *p;
-    size_t n;
-    ~WipeGuard() { wipe_dev(p, n); }
-};
+// bign_sign.c:32-245).  Secrets cross the staging buffer t_scr[3]: each entry marks them Stage::secret(), and they are overwritten
+// with zeros on every way out (early error returns, an allocation that throws).
 // host bytes that hold secrets: wiped on every way out of the scope, a return in mid-function and an exception included
 struct SecretVec {
     std::vector<octet> v;
@@ -580,28 +547,19 @@ try {
     if (code != ERR_OK) return code;
     if (n && (!privkeys || !pubkeys || !codes)) return ERR_BAD_INPUT;
     if (n == 0) return ERR_OK;
-    code = ensure_device();
-    if (code != ERR_OK) return code;
-    const size_t no = params->l / 4;
-    const size_t db = no * n, po = (db + 15) & ~(size_t)15, co = (po + 2 * no * n + 15) & ~(size_t)15;
-    Scratch &s = t_scr[3];
-    code = s.need(co + 4 * n);
-    if (code != ERR_OK) return code;
-    octet *d = (octet *)s.p;
-    const WipeGuard wipe{d, db};
-    B2H_TRY(h2d(d, privkeys, db));
-    code = pubkey_calc_any(params, false, d, n, d + po, d + co);
-    if (code == ERR_OK) {
-        hipError_t e = d2h(codes, d + co, 4 * n);
-        // bee2 leaves the output alone when it fails: copy the keys of the good items only
-        octet *tmp = new (std::nothrow) octet[2 * no * n];
-        if (!tmp) return ERR_OUTOFMEMORY;                       // (the guard above wipes the staged keys)
-        if (e == hipSuccess) e = d2h(tmp, d + po, 2 * no * n);
-        if (e != hipSuccess) code = hip_fail(e, "bignPubkeyCalc copy");
-        else for (size_t i = 0; i < n; ++i) if (codes[i] == ERR_OK) memcpy(pubkeys + 2 * no * i, tmp + 2 * no * i, 2 * no);
-        delete[] tmp;
-    }
-    return code;
+    const size_t no = params->l / 4, db = no * n;
+    Stage sg(3, false, "bee2hip_bignPubkeyCalc_batch staging");
+    const size_t o_d = sg.add(db), po = sg.add(2 * no * n), co = sg.add(4 * n);
+    sg.secret(o_d, db);
+    B2H_OK(sg.open());
+    B2H_OK(sg.in(o_d, privkeys, db));
+    B2H_OK(pubkey_calc_any(params, false, sg.at(o_d), n, sg.at(po), sg.at(co)));
+    B2H_OK(sg.out(codes, co, 4 * n));
+    // bee2 leaves the output alone when it fails: copy the keys of the good items only
+    std::vector<octet> tmp(2 * no * n);
+    B2H_OK(sg.out(tmp.data(), po, 2 * no * n));
+    for (size_t i = 0; i < n; ++i) if (codes[i] == ERR_OK) memcpy(pubkeys + 2 * no * i, tmp.data() + 2 * no * i, 2 * no);
+    return ERR_OK;
 } B2H_CATCH
 
 // mode 0: t (shared by the batch, may be null) -- bignSign2; mode 1: aux = one-time keys k[n][no] -- bignSign after its rng
@@ -614,19 +572,16 @@ static err_t sign_batch_host(int mode, const bign_params *params, const octet oi
     if (!oid_der_valid(oid_der, oid_len)) return ERR_BAD_OID;
     if (n == 0) return ERR_OK;
     if (mode == 0 && !aux) t_len = 0;
-    code = ensure_device();
-    if (code != ERR_OK) return code;
     const size_t no = params->l / 4, sg = no + no / 2;
     // theta = belt-hash(oid || d || t) for additional input beyond what the nonce kernel assembles itself (bign_sign.c:183-196): ONE
     // ragged belt-hash launch over the n messages (round 5, ADVICE r04: the streaming drop-ins took ~4 synchronous GPU round trips
     // per signature -- tens of seconds at 2^18 -- and could only abort on a device fault).  The messages hold the private keys: the
-    // host copy lives in a vector that wipes itself on every way out, the device copy under a WipeGuard.
+    // host copy lives in a vector that wipes itself on every way out, the device copy in a Stage::secret() range.
     SecretVec theta;
     int dev_mode = mode;
     size_t ab = mode == 1 ? no * n : t_len;
     if (mode == 0 && t_len > 64) {
         const size_t ml = oid_len + no + t_len;
-        const size_t o_off = (n * ml + 15) & ~(size_t)15, o_th = (o_off + 8 * (n + 1) + 15) & ~(size_t)15;
         SecretVec msgs;
         msgs.v.resize(n * ml);
         for (size_t i = 0; i < n; ++i) {
@@ -637,49 +592,39 @@ static err_t sign_batch_host(int mode, const bign_params *params, const octet oi
         }
         std::vector<uint64_t> off(n + 1);
         for (size_t i = 0; i <= n; ++i) off[i] = (uint64_t)i * ml;
-        Scratch &ts = t_scr[2];
-        code = ts.need(o_th + 32 * n + 16);
-        if (code != ERR_OK) return code;
-        octet *td = (octet *)ts.p;
-        const WipeGuard wipe_msgs{td, o_th + 32 * n};
-        B2H_TRY(h2d(td, msgs.v.data(), n * ml));
-        B2H_TRY(h2d(td + o_off, off.data(), 8 * (n + 1)));
-        code = launch_hash_ragged(0, td, td + o_off, nullptr, n, td + o_th, nullptr, true);     // (bank-private table: the messages hold d)
-        if (code != ERR_OK) return code;
+        Stage ts(2, false, "bignSign2 theta staging");
+        const size_t o_msg = ts.add(n * ml), o_off = ts.add(8 * (n + 1)), o_th = ts.add(32 * n);
+        ts.secret(o_msg, o_th + 32 * n);
+        B2H_OK(ts.open(16));
+        B2H_OK(ts.in(o_msg, msgs.v.data(), n * ml));
+        B2H_OK(ts.in(o_off, off.data(), 8 * (n + 1)));
+        B2H_OK(launch_hash_ragged(0, ts.at(o_msg), ts.at(o_off), nullptr, n, ts.at(o_th), nullptr, true));   // (bank-private table: the messages hold d)
         theta.v.resize(32 * n);
-        B2H_TRY(d2h(theta.v.data(), td + o_th, 32 * n));
+        B2H_OK(ts.out(theta.v.data(), o_th, 32 * n));
         aux = theta.v.data();
         ab = 32 * n;
         dev_mode = 2;
     }
     const size_t hb = no * n;
-    const size_t o_d = (hb + 15) & ~(size_t)15, o_a = (o_d + hb + 15) & ~(size_t)15, o_s = (o_a + ab + 15) & ~(size_t)15,
-                 o_c = (o_s + sg * n + 15) & ~(size_t)15;
-    Scratch &s = t_scr[3];
-    code = s.need(o_c + 4 * n);
-    if (code != ERR_OK) return code;
-    octet *d = (octet *)s.p;
-    const WipeGuard wipe{d + o_d, o_s - o_d};              // private keys and one-time keys / t / theta
-    B2H_TRY(h2d(d, hashes, hb));
-    B2H_TRY(h2d(d + o_d, privkeys, hb));
-    if (ab) B2H_TRY(h2d(d + o_a, aux, ab));
-    {
-        bool standard;
-        code = params_check_sign(params, &standard);
-        if (code == ERR_OK)
-            code = standard ? launch_bign_sign(params->l, dev_mode, oid_der, oid_len, d, d + o_d, ab ? d + o_a : nullptr, t_len, 1, n,
-                                               d + o_s, d + o_c, nullptr)
-                            : launch_bign_sign_generic(params, dev_mode, oid_der, oid_len, d, d + o_d, ab ? d + o_a : nullptr, t_len, 1,
-                                                       n, d + o_s, d + o_c, nullptr);
-    }
-    if (code == ERR_OK) {
-        hipError_t e = d2h(codes, d + o_c, 4 * n);
-        std::vector<octet> tmp(sg * n);
-        if (e == hipSuccess) e = d2h(tmp.data(), d + o_s, sg * n);
-        if (e != hipSuccess) code = hip_fail(e, "bignSign copy");
-        else for (size_t i = 0; i < n; ++i) if (codes[i] == ERR_OK) memcpy(sigs + sg * i, tmp.data() + sg * i, sg);
-    }
-    return code;
+    Stage st(3, false, "bignSign batch staging");
+    const size_t o_h = st.add(hb), o_d = st.add(hb), o_a = st.add(ab), o_s = st.add(sg * n), o_c = st.add(4 * n);
+    st.secret(o_d, o_s - o_d);                             // private keys and one-time keys / t / theta
+    B2H_OK(st.open());
+    B2H_OK(st.in(o_h, hashes, hb));
+    B2H_OK(st.in(o_d, privkeys, hb));
+    B2H_OK(st.in(o_a, aux, ab));
+    octet *d_aux = ab ? st.at(o_a) : nullptr;
+    bool standard;
+    B2H_OK(params_check_sign(params, &standard));
+    B2H_OK(standard ? launch_bign_sign(params->l, dev_mode, oid_der, oid_len, st.at(o_h), st.at(o_d), d_aux, t_len, 1, n, st.at(o_s),
+                                       st.at(o_c), nullptr)
+                    : launch_bign_sign_generic(params, dev_mode, oid_der, oid_len, st.at(o_h), st.at(o_d), d_aux, t_len, 1, n,
+                                               st.at(o_s), st.at(o_c), nullptr));
+    B2H_OK(st.out(codes, o_c, 4 * n));
+    std::vector<octet> tmp(sg * n);
+    B2H_OK(st.out(tmp.data(), o_s, sg * n));
+    for (size_t i = 0; i < n; ++i) if (codes[i] == ERR_OK) memcpy(sigs + sg * i, tmp.data() + sg * i, sg);
+    return ERR_OK;
 }
 extern "C" err_t bee2hip_bignSign2_batch(const bign_params *params, const octet oid_der[], size_t oid_len, const octet *hashes,
                                          const octet *privkeys, const void *t, size_t t_len, size_t n, octet *sigs, err_t *codes)
@@ -689,9 +634,7 @@ try {
 extern "C" err_t bee2hip_bignSignK_batch(const bign_params *params, const octet oid_der[], size_t oid_len, const octet *hashes,
                                          const octet *privkeys, const octet *ks, size_t n, octet *sigs, err_t *codes)
 try {
-    try {
-        return sign_batch_host(1, params, oid_der, oid_len, hashes, privkeys, ks, 0, n, sigs, codes);
-    } catch (const std::bad_alloc &) { return ERR_OUTOFMEMORY; }
+    return sign_batch_host(1, params, oid_der, oid_len, hashes, privkeys, ks, 0, n, sigs, codes);
 } B2H_CATCH
 
 // ---- drop-ins.  Order of checks as the reference: parameters (bignParamsCheck), pointers, OID, private key.
@@ -726,6 +669,23 @@ static bool rand_nz_mod(octet *a, const octet *mod, size_t no, gen_i rng, void *
     }
     return false;
 }
+// Q = d G on the GPU for ONE private key d (64 octets of host buffer); the outputs are written on success only
+static err_t keypair_gen_gpu(const bign_params *params, const octet d[64], octet privkey[], octet pubkey[])
+{
+    const size_t no = params->l / 4;
+    Stage sg(3, false, "bignKeypairGen staging");
+    const size_t o_d = sg.add(64), o_q = sg.add(128), o_c = sg.add(16);
+    sg.secret(o_d, 64);
+    B2H_OK(sg.open());
+    B2H_OK(sg.in(o_d, d, no));
+    B2H_OK(pubkey_calc_any(params, true, sg.at(o_d), 1, sg.at(o_q), sg.at(o_c)));
+    octet q[128];
+    err_t one = ERR_BAD_PARAMS;
+    B2H_OK(sg.out(q, o_q, 2 * no));
+    B2H_OK(sg.out(&one, o_c, 4));
+    if (one == ERR_OK) { memcpy(privkey, d, no); memcpy(pubkey, q, 2 * no); }
+    return one;                                                  // ERR_BAD_PARAMS when d G = O (bign_misc.c:214-218)
+}
 extern "C" err_t bignKeypairGen(octet privkey[], octet pubkey[], const bign_params *params, gen_i rng, void *rng_state)
 try {
     err_t code = params_check(params);
@@ -746,28 +706,8 @@ try {
         wipe_host(d, sizeof d);
         return code;
     }
-    if (code == ERR_OK) {
-        Scratch &s = t_scr[3];
-        code = s.need(64 + 128 + 16);
-        if (code == ERR_OK) {
-            octet *dd = (octet *)s.p;
-            hipError_t e = h2d(dd, d, no);
-            if (e == hipSuccess) {
-                code = pubkey_calc_any(params, true, dd, 1, dd + 64, dd + 192);
-                octet q[128];
-                err_t one = ERR_BAD_PARAMS;
-                if (code == ERR_OK) e = d2h(q, dd + 64, 2 * no);
-                if (code == ERR_OK && e == hipSuccess) e = d2h(&one, dd + 192, 4);
-                if (code == ERR_OK && e == hipSuccess) {
-                    code = one;                                  // ERR_BAD_PARAMS when d G = O (bign_misc.c:214-218)
-                    if (one == ERR_OK) { memcpy(privkey, d, no); memcpy(pubkey, q, 2 * no); }
-                }
-            }
-            if (e != hipSuccess) code = hip_fail(e, "bignKeypairGen copy");
-            wipe_dev(dd, 64);
-        }
-    }
-    memset(d, 0, sizeof d);
+    if (code == ERR_OK) code = keypair_gen_gpu(params, d, privkey, pubkey);
+    wipe_host(d, sizeof d);
     return code;
 } B2H_CATCH
 extern "C" err_t bignSign(octet sig[], const bign_params *params, const octet oid_der[], size_t oid_len, const octet hash[],

@@ -8,7 +8,7 @@ try {
     if (misaligned(d_msgs, 16)) return ERR_BAD_INPUT;
     const bool do_hash = d_digests != nullptr, do_mac = d_tags != nullptr;
     if (do_hash && (l == 0 || l % 16 != 0 || l > 256)) return ERR_BAD_PARAMS;      // bash_hash.c:122-123
-    if (do_mac && ((key_len != 16 && key_len != 24 && key_len != 32) || !key)) return ERR_BAD_INPUT;
+    if (do_mac && (!key_len_ok(key_len) || !key)) return ERR_BAD_INPUT;
     if (n && msg_len && !d_msgs) return ERR_BAD_INPUT;
     err_t code = ensure_device();
     if (code != ERR_OK) return code;
@@ -23,21 +23,18 @@ extern "C" err_t bee2hip_bashHash_beltMAC_batch(const octet *msgs, size_t msg_le
                                                 octet *digests, octet *tags)
 try {
     if (digests && (l == 0 || l % 16 != 0 || l > 256)) return ERR_BAD_PARAMS;
-    if (tags && ((key_len != 16 && key_len != 24 && key_len != 32) || !key)) return ERR_BAD_INPUT;
+    if (tags && (!key_len_ok(key_len) || !key)) return ERR_BAD_INPUT;
     if (n && msg_len && !msgs) return ERR_BAD_INPUT;
     if (n == 0) return ERR_OK;
     const size_t dlen = digests ? l / 4 : 0;
-    const size_t in_b = (n * msg_len + 15) & ~(size_t)15, dg_b = (n * dlen + 15) & ~(size_t)15;
-    Scratch &s = t_scr[3];
-    err_t code = s.need(in_b + dg_b + n * 8 + 16);
-    if (code != ERR_OK) return code;
-    octet *d = (octet *)s.p;
-    if (n * msg_len) B2H_TRY(h2d(d, msgs, n * msg_len));
-    code = bee2hip_bashHash_beltMAC_batch_dev(d, msg_len, n, l, key, key_len, digests ? d + in_b : nullptr,
-                                              tags ? d + in_b + dg_b : nullptr, nullptr);
-    if (code != ERR_OK) return code;
-    if (digests) B2H_TRY(d2h(digests, d + in_b, n * dlen));
-    if (tags) B2H_TRY(d2h(tags, d + in_b + dg_b, n * 8));
+    Stage sg(3, false, "bee2hip_bashHash_beltMAC_batch staging");
+    const size_t o_in = sg.add(n * msg_len), o_dg = sg.add(n * dlen), o_tag = sg.add(n * 8);
+    B2H_OK(sg.open(16));
+    B2H_OK(sg.in(o_in, msgs, n * msg_len));
+    B2H_OK(bee2hip_bashHash_beltMAC_batch_dev(sg.at(o_in), msg_len, n, l, key, key_len, digests ? sg.at(o_dg) : nullptr,
+                                              tags ? sg.at(o_tag) : nullptr, nullptr));
+    if (digests) B2H_OK(sg.out(digests, o_dg, n * dlen));
+    if (tags) B2H_OK(sg.out(tags, o_tag, n * 8));
     return ERR_OK;
 } B2H_CATCH
 
@@ -160,14 +157,11 @@ static err_t hash_ragged_host(size_t alg, const octet *data, const uint64_t *off
         for (size_t t = 0; t < std::min(T, K); ++t) workers.emplace_back(host_job);
     }
     const size_t ng = n - K;                                               // slots of the GPU launch: ord[K .. n)
-    const size_t ob = (n + 1) * 8, oo = (total + 15) & ~(size_t)15, ro = (oo + ob + 15) & ~(size_t)15,
-                 go = (ro + n * 4 + 15) & ~(size_t)15;
-    Scratch &s = t_scr[3];
-    err_t code = s.need(go + n * dlen + 16);
-    if (code != ERR_OK) return code;
-    octet *d = (octet *)s.p;
+    Stage sg(3, false, "bee2hip_hash_ragged staging");
+    const size_t o_data = sg.add(total), oo = sg.add((n + 1) * 8), ro = sg.add(n * 4), go = sg.add(n * dlen);
+    B2H_OK(sg.open(16));
     if (K == 0) {
-        if (total) B2H_TRY(h2d(d, data, total));
+        B2H_OK(sg.in(o_data, data, total));
     } else {
         // the K messages the host threads take are not uploaded: the runs of octets between them go up one by one (the device
         // layout is the caller's, with holes nobody reads)
@@ -176,15 +170,14 @@ static err_t hash_ragged_host(size_t alg, const octet *data, const uint64_t *off
         uint64_t from = 0;
         for (size_t k = 0; k <= K; ++k) {
             const uint64_t to = k < K ? offsets[host_ix[k]] : (uint64_t)total;
-            if (to > from) B2H_TRY(h2d(d + from, data + from, (size_t)(to - from)));
+            if (to > from) B2H_OK(sg.in(o_data + (size_t)from, data + from, (size_t)(to - from)));
             if (k < K) from = offsets[host_ix[k] + 1];
         }
     }
-    B2H_TRY(h2d(d + oo, offsets, ob));
-    B2H_TRY(h2d(d + ro, ord.data() + K, ng * 4));
-    code = bee2hip_hash_ragged_ordered_dev(alg, d, d + oo, d + ro, ng, d + go, nullptr);
-    if (code != ERR_OK) return code;
-    B2H_TRY(d2h(digests, d + go, n * dlen));
+    B2H_OK(sg.in(oo, offsets, (n + 1) * 8));
+    B2H_OK(sg.in(ro, ord.data() + K, ng * 4));
+    B2H_OK(bee2hip_hash_ragged_ordered_dev(alg, sg.at(o_data), sg.at(oo), sg.at(ro), ng, sg.at(go), nullptr));
+    B2H_OK(sg.out(digests, go, n * dlen));
     for (std::thread &t : workers) t.join();
     for (size_t k = 0; k < K; ++k) memcpy(digests + (size_t)ord[k] * dlen, hdig.data() + k * dlen, dlen);
     return ERR_OK;

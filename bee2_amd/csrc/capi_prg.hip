@@ -85,7 +85,6 @@ static void prg_longest_first(std::vector<uint32_t> &ord, const uint64_t *offset
         return offsets[a + 1] - offsets[a] > offsets[b + 1] - offsets[b];
     });
 }
-static inline size_t prg_up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 extern "C" err_t bee2hip_bashPrgHash_ragged(size_t l, size_t d, const octet ann[], size_t ann_len, const octet *data,
                                             const uint64_t *offsets, size_t n, octet *out, size_t out_len)
@@ -96,26 +95,21 @@ try {
     if (!offsets || !out || !prg_offsets_ok(offsets, n)) return ERR_BAD_INPUT;
     const size_t first = (size_t)offsets[0], total = (size_t)(offsets[n] - offsets[0]);
     if (total && !data) return ERR_BAD_INPUT;
-    code = ensure_device();
-    if (code != ERR_OK) return code;
     std::vector<uint32_t> ord;
     prg_longest_first(ord, offsets, n);
     // the data keeps its alignment mod 16 (first & 15 octets of slack in front), offsets are rebased to the staging block
-    const size_t lead = first & 15, o_off = prg_up16(lead + total), o_ord = o_off + prg_up16((n + 1) * 8),
-                 o_out = o_ord + prg_up16(n * 4);
-    Scratch &s = t_scr[3];
-    code = s.need(o_out + n * out_len + 16);
-    if (code != ERR_OK) return code;
-    octet *dv = (octet *)s.p;
+    const size_t lead = first & 15;
+    Stage sg(3, false, "bee2hip_bashPrgHash_ragged staging");
+    const size_t o_data = sg.add(lead + total), o_off = sg.add((n + 1) * 8), o_ord = sg.add(n * 4), o_out = sg.add(n * out_len);
+    B2H_OK(sg.open(16));
     std::vector<uint64_t> off(n + 1);
     for (size_t i = 0; i <= n; ++i) off[i] = offsets[i] - first + lead;
-    if (total) B2H_TRY(h2d(dv + lead, data + first, total));
-    B2H_TRY(h2d(dv + o_off, off.data(), (n + 1) * 8));
-    B2H_TRY(h2d(dv + o_ord, ord.data(), n * 4));
-    code = bee2hip_bashPrgHash_ragged_stream(l, d, ann, ann_len, dv, dv + o_off, dv + o_ord, n, dv + o_out, out_len, nullptr);
-    if (code != ERR_OK) return code;
-    B2H_TRY(d2h(out, dv + o_out, n * out_len));
-    return ERR_OK;
+    if (total) B2H_OK(sg.in(o_data + lead, data + first, total));          // (data may be null when there is no text at all)
+    B2H_OK(sg.in(o_off, off.data(), (n + 1) * 8));
+    B2H_OK(sg.in(o_ord, ord.data(), n * 4));
+    B2H_OK(bee2hip_bashPrgHash_ragged_stream(l, d, ann, ann_len, sg.at(o_data), sg.at(o_off), sg.at(o_ord), n, sg.at(o_out), out_len,
+                                             nullptr));
+    return sg.out(out, o_out, n * out_len);
 } B2H_CATCH
 
 static err_t prg_ae_host(int unwrap, size_t l, size_t d, const octet key[], size_t key_len, const octet *anns, size_t ann_len,
@@ -130,39 +124,31 @@ static err_t prg_ae_host(int unwrap, size_t l, size_t d, const octet key[], size
     const size_t first = (size_t)offsets[0], total = (size_t)(offsets[n] - offsets[0]);
     const size_t hfirst = hdr_offsets ? (size_t)hdr_offsets[0] : 0, htotal = hdr_offsets ? (size_t)(hdr_offsets[n] - hdr_offsets[0]) : 0;
     if ((total && (!src || !dst)) || (htotal && !hdrs)) return ERR_BAD_INPUT;
-    code = ensure_device();
-    if (code != ERR_OK) return code;
     std::vector<uint32_t> ord;
     prg_longest_first(ord, offsets, n);
     const size_t lead = first & 15, hlead = hfirst & 15;
-    const size_t o_hdr = prg_up16(lead + total), o_ann = o_hdr + prg_up16(hlead + htotal), o_off = o_ann + prg_up16(n * ann_len),
-                 o_hoff = o_off + prg_up16((n + 1) * 8), o_ord = o_hoff + prg_up16((n + 1) * 8), o_tag = o_ord + prg_up16(n * 4),
-                 o_code = o_tag + prg_up16(n * tag_len);
-    Scratch &s = t_scr[3];
-    code = s.need(o_code + n * 4 + 16);
-    if (code != ERR_OK) return code;
-    octet *dv = (octet *)s.p;
+    Stage sg(3, false, "bee2hip_bashPrgAE staging");
+    const size_t o_txt = sg.add(lead + total), o_hdr = sg.add(hlead + htotal), o_ann = sg.add(n * ann_len), o_off = sg.add((n + 1) * 8),
+                 o_hoff = sg.add((n + 1) * 8), o_ord = sg.add(n * 4), o_tag = sg.add(n * tag_len), o_code = sg.add(n * 4);
+    B2H_OK(sg.open(16));
     std::vector<uint64_t> off(n + 1);
     for (size_t i = 0; i <= n; ++i) off[i] = offsets[i] - first + lead;
-    B2H_TRY(h2d(dv + o_off, off.data(), (n + 1) * 8));
+    B2H_OK(sg.in(o_off, off.data(), (n + 1) * 8));
     if (hdr_offsets) {
         for (size_t i = 0; i <= n; ++i) off[i] = hdr_offsets[i] - hfirst + hlead;
-        B2H_TRY(h2d(dv + o_hoff, off.data(), (n + 1) * 8));
-        if (htotal) B2H_TRY(h2d(dv + o_hdr + hlead, hdrs + hfirst, htotal));
+        B2H_OK(sg.in(o_hoff, off.data(), (n + 1) * 8));
+        if (htotal) B2H_OK(sg.in(o_hdr + hlead, hdrs + hfirst, htotal));
     }
-    if (total) B2H_TRY(h2d(dv + lead, src + first, total));
-    if (ann_len) B2H_TRY(h2d(dv + o_ann, anns, n * ann_len));
-    if (unwrap) B2H_TRY(h2d(dv + o_tag, tags, n * tag_len));
-    B2H_TRY(h2d(dv + o_ord, ord.data(), n * 4));
+    if (total) B2H_OK(sg.in(o_txt + lead, src + first, total));
+    B2H_OK(sg.in(o_ann, anns, n * ann_len));
+    if (unwrap) B2H_OK(sg.in(o_tag, tags, n * tag_len));
+    B2H_OK(sg.in(o_ord, ord.data(), n * 4));
     // in place on the device: the text is staged once
-    code = bee2hip_bashPrgAE_ragged_stream(unwrap, l, d, key, key_len, dv + o_ann, ann_len, hdr_offsets ? dv + o_hdr : nullptr,
-                                           hdr_offsets ? dv + o_hoff : nullptr, dv, dv + o_off, dv + o_ord, n, dv, dv + o_tag,
-                                           tag_len, unwrap ? dv + o_code : nullptr, nullptr);
-    if (code != ERR_OK) return code;
-    if (total) B2H_TRY(d2h(dst + first, dv + lead, total));
-    if (unwrap) B2H_TRY(d2h(codes, dv + o_code, n * 4));
-    else B2H_TRY(d2h(tags, dv + o_tag, n * tag_len));
-    return ERR_OK;
+    B2H_OK(bee2hip_bashPrgAE_ragged_stream(unwrap, l, d, key, key_len, sg.at(o_ann), ann_len, hdr_offsets ? sg.at(o_hdr) : nullptr,
+                                           hdr_offsets ? sg.at(o_hoff) : nullptr, sg.at(o_txt), sg.at(o_off), sg.at(o_ord), n,
+                                           sg.at(o_txt), sg.at(o_tag), tag_len, unwrap ? sg.at(o_code) : nullptr, nullptr));
+    if (total) B2H_OK(sg.out(dst + first, o_txt + lead, total));
+    return unwrap ? sg.out(codes, o_code, n * 4) : sg.out(tags, o_tag, n * tag_len);
 }
 
 extern "C" err_t bee2hip_bashPrgAE_wrap_ragged(size_t l, size_t d, const octet key[], size_t key_len, const octet *anns,

@@ -298,6 +298,49 @@ static inline hipError_t zero_staging(void *d, size_t n)
     return hipMemset(d, 0, n);
 }
 
+// One staged call of a host-pointer entry point (DESIGN.md 1 "Staging"): the parts of thread-local slot `slot` in the order they are
+// add()ed, each at the next 16-aligned offset (the kernels read blocks, states and field elements as 16-byte vectors); open()
+// makes the device ready and the slot large enough, in() / out() copy a part, and a range marked secret() is zeroed when the
+// Stage goes, on every way out of the entry -- a return in mid-function and an exception included.
+#define B2H_OK(call)                                                    \
+    do {                                                                \
+        const err_t c_ = (call);                                        \
+        if (c_ != ERR_OK) return c_;                                    \
+    } while (0)
+static inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+class Stage {
+    Scratch &s;
+    const bool chain;
+    const char *const what;                     // the entry, for bee2hip_last_error()
+    octet *base = nullptr;                      // set by open(): nothing is staged, copied or wiped before
+    size_t total = 0, sec_off = 0, sec_n = 0;
+public:
+    Stage(int slot, bool chain_, const char *what_) : s(t_scr[slot]), chain(chain_), what(what_) {}
+    Stage(const Stage &) = delete;
+    ~Stage() { if (base && sec_n) (void)zero_staging(base + sec_off, sec_n); }
+    size_t add(size_t bytes) { const size_t off = up16(total); total = off + bytes; return off; }
+    void secret(size_t off, size_t n) { sec_off = off; sec_n = n; }
+    // `slack`: octets past the last part that a kernel may touch (DESIGN.md 1 "Staging" says which sites have some)
+    err_t open(size_t slack = 0)
+    {
+        B2H_OK(ensure_device());
+        B2H_OK(s.need(total + slack, chain));
+        base = (octet *)s.p;
+        return ERR_OK;
+    }
+    octet *at(size_t off) const { return base + off; }
+    err_t in(size_t off, const void *host, size_t n)
+    {
+        const hipError_t e = n ? h2d(base + off, host, n) : hipSuccess;
+        return e == hipSuccess ? ERR_OK : hip_fail(e, what);
+    }
+    err_t out(void *host, size_t off, size_t n)
+    {
+        const hipError_t e = n ? d2h(host, base + off, n) : hipSuccess;
+        return e == hipSuccess ? ERR_OK : hip_fail(e, what);
+    }
+};
+
 
 // ------------------------------------------------- host path for small single calls ---
 // host_small.hpp has the what and why.  Who runs where:

@@ -192,6 +192,110 @@ static void worker_pool()
     CHECK(m == m1 && !memcmp(&a, &b, sizeof a));
 }
 
+// ---- Stage: layout, pinned / device choice, the round trip through both, zero-length copies, secrets on every way out ----
+// a staged call as the entries write them: two inputs and an output, the first input secret; `how` picks the way out
+// (0 return at the end, 1 early error return, 2 std::bad_alloc); *where = the staging block, for the caller to inspect afterwards
+static err_t staged_call(size_t na, size_t nb, const octet *a, const octet *b, octet *out, int how, octet **where, size_t *o_sec)
+{
+    Stage sg(1, false, "stage_helper");
+    const size_t o_a = sg.add(na), o_b = sg.add(nb), o_out = sg.add(na + nb);
+    sg.secret(o_a, na);
+    B2H_OK(sg.open(16));
+    *where = sg.at(0);
+    *o_sec = o_a;
+    B2H_OK(sg.in(o_a, a, na));
+    B2H_OK(sg.in(o_b, b, nb));
+    if (how == 1) return ERR_BAD_INPUT;
+    if (how == 2) throw std::bad_alloc();
+    octet *pa = sg.at(o_a), *pb = sg.at(o_b), *po = sg.at(o_out);
+    mockhipLaunch(nullptr, [=] { for (size_t i = 0; i < na; ++i) po[i] = tf(pa[i], i); for (size_t i = 0; i < nb; ++i) po[na + i] = tf(pb[i], na + i); });
+    return sg.out(out, o_out, na + nb);
+}
+static void stage_helper()
+{
+    // offsets: 16-aligned, in the order added, no overlap, and what the chained (x + 15) & ~15 of the entries gave
+    const size_t orders[][6] = {{0, 1, 15, 16, 17, 4097}, {4097, 17, 16, 15, 1, 0}, {16, 0, 4097, 1, 17, 15}, {15, 4097, 0, 17, 16, 1},
+                                {1, 1, 16, 16, 0, 0}};
+    for (const auto &order : orders) {
+        Stage sg(0, false, "stage_helper");
+        size_t hand = 0, end = 0;
+        for (const size_t n : order) {
+            const size_t off = sg.add(n);
+            hand = (hand + 15) & ~(size_t)15;
+            CHECK(off == hand && off % 16 == 0 && off >= end && up16(off) == off);
+            hand += n;
+            end = off + n;
+        }
+        g_pinned_limit = end + 8;                              // the byte count open() asks for is the hand formula's total + the slack
+        CHECK(sg.open(8) == ERR_OK && in_pinned(sg.at(0)));
+        g_pinned_limit = end + 7;
+        CHECK(sg.open(8) == ERR_OK && !in_pinned(sg.at(0)));
+        g_pinned_limit = PINNED_MAX;
+    }
+    // pinned or device: the byte count given to need() decides, to the byte
+    const auto where = [](size_t total, size_t slack, bool chain) {
+        Stage sg(2, chain, "stage_helper");
+        sg.add(total - slack);
+        CHECK(sg.open(slack) == ERR_OK);
+        return in_pinned(sg.at(0));
+    };
+    CHECK(where(PINNED_MAX, 0, false) && !where(PINNED_MAX + 1, 0, false));
+    CHECK(where(PINNED_MAX, 16, false) && !where(PINNED_MAX + 1, 16, false));
+    CHECK(where(2048, 0, true) && !where(2049, 0, true) && where(2048, 16, true) && !where(2049, 16, true));
+    g_pinned_limit = 0;
+    CHECK(!where(1, 0, false) && !where(16, 16, true) && !where(PINNED_MAX, 0, false));
+    g_pinned_limit = PINNED_MAX;
+    // round trip, secrets and exits in both modes
+    for (int device = 0; device < 2; ++device) {
+        g_pinned_limit = device ? 0 : PINNED_MAX;
+        const size_t shapes[][2] = {{1, 0}, {15, 17}, {16, 16}, {17, 4097}, {0, 33}};
+        for (const auto &sh : shapes) {
+            const size_t na = sh[0], nb = sh[1];
+            std::vector<octet> a(na), b(nb), out(na + nb, 0xEE), want(na + nb);
+            fill(a, 11); fill(b, 12);
+            for (size_t i = 0; i < na; ++i) a[i] |= 1;         // (no zero octet in the secret: a wipe shows)
+            for (size_t i = 0; i < na + nb; ++i) want[i] = tf(i < na ? a[i] : b[i - na], i);
+            for (int how = 0; how < 3; ++how) {
+                octet *blk = nullptr;
+                size_t o_sec = 0;
+                std::fill(out.begin(), out.end(), 0xEE);
+                err_t code = ERR_OK;
+                try { code = staged_call(na, nb, a.data(), b.data(), out.data(), how, &blk, &o_sec); }
+                catch (const std::bad_alloc &) { CHECK(how == 2); code = ERR_OUTOFMEMORY; }
+                CHECK(code == (how == 0 ? ERR_OK : how == 1 ? ERR_BAD_INPUT : ERR_OUTOFMEMORY));
+                CHECK(in_pinned(blk) == !device);
+                if (how == 0) CHECK(out == want);
+                else for (octet x : out) CHECK(x == 0xEE);
+                // the staging block afterwards: the secret part reads zero, the part behind it is what was staged
+                std::vector<octet> img(up16(na) + nb);
+                CHECK(hipMemcpy(img.data(), blk, img.size(), hipMemcpyDeviceToHost) == hipSuccess);
+                for (size_t i = 0; i < na; ++i) CHECK(img[o_sec + i] == 0);
+                for (size_t i = 0; i < nb; ++i) CHECK(img[up16(na) + i] == b[i]);
+            }
+        }
+    }
+    {   // zero-length in / out touch nothing, null host pointers included
+        Stage sg(1, false, "stage_helper");
+        const size_t o = sg.add(32);
+        CHECK(sg.open() == ERR_OK);
+        memset(sg.at(o), 0x5A, 32);
+        CHECK(sg.in(o, nullptr, 0) == ERR_OK && sg.out(nullptr, o, 0) == ERR_OK);
+        for (size_t i = 0; i < 32; ++i) CHECK(sg.at(o)[i] == 0x5A);
+    }
+    {   // open() refused: ERR_OUTOFMEMORY, and the Stage that marked a secret goes without dereferencing anything
+        g_pinned_limit = 0;
+        octet *blk = nullptr;
+        size_t o_sec = 0;
+        octet a[16] = {1}, b[1] = {2}, out[17];
+        mockhip::g().malloc_fail_in.store(1);
+        // (slot 1 holds fewer than 1 MiB: the request has to allocate)
+        std::vector<octet> big(1 << 20), big_out(16 + big.size());
+        CHECK(staged_call(16, big.size(), a, big.data(), big_out.data(), 0, &blk, &o_sec) == ERR_OUTOFMEMORY && blk == nullptr);
+        CHECK(staged_call(16, 1, a, b, out, 0, &blk, &o_sec) == ERR_OK && blk != nullptr);
+        g_pinned_limit = PINNED_MAX;
+    }
+}
+
 int main()
 {
     CHECK(ensure_device() == ERR_OK);
@@ -210,6 +314,7 @@ int main()
         for (auto &t : th) t.join();
     }
     pool_and_fallback();
+    stage_helper();
     worker_pool();
     CHECK(hipDeviceSynchronize() == hipSuccess);
     puts("staging mock ok");
