@@ -15,7 +15,7 @@
 //   (tools/ubench): per SIMD a block costs ~2.5 cycles per VALU op plus
 //   ~3.7 issue cycles per ds_read_b32 -- VALU and LDS issue do not overlap within a SIMD.
 //
-// belt_encr_blocks_kernel : E_K over n blocks in place (ctr0 = E_K(iv) of
+// belt_blocks_kernel : E_K (or D_K) over n blocks in place (ctr0 = E_K(iv) of
 //   beltCTRStart, belt_ctr.c:55-64; r = E_K(0) of beltMACStart, belt_mac.c:47-56;
 //   the drop-in beltBlockEncr*).
 #include <algorithm>
@@ -123,8 +123,10 @@ void beltCTR_blocks_kernel(uint4 *__restrict__ buf, size_t nblocks, BeltKey key,
     }
 }
 
+// one kernel for both directions: the helper runs only in 64-thread launches of a handful of blocks, and the direction is
+// a launch argument the whole grid agrees on
 __global__ __launch_bounds__(64)
-void belt_encr_blocks_kernel(uint4 *__restrict__ blocks, size_t nblocks, BeltKey key)
+void belt_blocks_kernel(uint4 *__restrict__ blocks, size_t nblocks, BeltKey key, int decr)
 {
     __shared__ __attribute__((aligned(16))) uint8_t smem[BeltTabSmall::kBytes];
     BeltTabSmall::fill(smem, threadIdx.x, 64);
@@ -137,7 +139,8 @@ void belt_encr_blocks_kernel(uint4 *__restrict__ blocks, size_t nblocks, BeltKey
     if (i >= nblocks) return;
     const uint4 v = blocks[i];
     uint32_t x[4] = {v.x, v.y, v.z, v.w};
-    belt_encr(T, x, K);
+    if (decr) belt_decr(T, x, K);
+    else belt_encr(T, x, K);
     blocks[i] = make_uint4(x[0], x[1], x[2], x[3]);
 }
 
@@ -602,24 +605,6 @@ void belt_cbc_encr_kernel(uint4 *__restrict__ msgs, size_t nblk, size_t n, BeltK
     ivs[m] = make_uint4(x[0], x[1], x[2], x[3]);
 }
 
-__global__ __launch_bounds__(64)
-void belt_decr_blocks_kernel(uint4 *__restrict__ blocks, size_t nblocks, BeltKey key)
-{
-    __shared__ __attribute__((aligned(16))) uint8_t smem[BeltTabSmall::kBytes];
-    BeltTabSmall::fill(smem, threadIdx.x, 64);
-    __syncthreads();
-    const BeltTabSmall T(smem);
-    uint32_t K[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) K[i] = key.k[i];
-    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (i >= nblocks) return;
-    const uint4 v = blocks[i];
-    uint32_t x[4] = {v.x, v.y, v.z, v.w};
-    belt_decr(T, x, K);
-    blocks[i] = make_uint4(x[0], x[1], x[2], x[3]);
-}
-
 // per-device launch facts (several devices may be driven from one process)
 static int g_num_cus[64];
 int cur_dev()
@@ -902,8 +887,8 @@ err_t launch_belt_decr_blocks(void *d_blocks, size_t nblocks, const uint32_t key
     if (nblocks == 0) return ERR_OK;
     BeltKey k;
     for (int i = 0; i < 8; ++i) k.k[i] = key[i];
-    hipLaunchKernelGGL(belt_decr_blocks_kernel, dim3((unsigned)((nblocks + 63) / 64)), dim3(64), 0, st,
-                       (uint4 *)d_blocks, nblocks, k);
+    hipLaunchKernelGGL(belt_blocks_kernel, dim3((unsigned)((nblocks + 63) / 64)), dim3(64), 0, st,
+                       (uint4 *)d_blocks, nblocks, k, 1);
     B2H_TRY(hipGetLastError());
     return ERR_OK;
 }
@@ -915,8 +900,8 @@ err_t launch_belt_encr_blocks(void *d_blocks, size_t nblocks, const uint32_t key
     for (int i = 0; i < 8; ++i) k.k[i] = key[i];
     const size_t grid = (nblocks + 63) / 64;
     if (grid > 0x7fffffffull) return ERR_BAD_INPUT;
-    hipLaunchKernelGGL(belt_encr_blocks_kernel, dim3((unsigned)grid), dim3(64), 0, st,
-                       (uint4 *)d_blocks, nblocks, k);
+    hipLaunchKernelGGL(belt_blocks_kernel, dim3((unsigned)grid), dim3(64), 0, st,
+                       (uint4 *)d_blocks, nblocks, k, 0);
     B2H_TRY(hipGetLastError());
     return ERR_OK;
 }

@@ -14,6 +14,7 @@
 //   capi_mixed.hip  bash + belt-MAC per message, ragged hash batches, path policy
 //   capi_prg.hip    bash-prg (prg-hash, prg-ae) over ragged batches
 //   capi_beltae.hip belt-dwp / belt-che over ragged batches of records
+//   capi_fmt.hip    belt-fmt over batches of records, beltFMTEncr / beltFMTDecr
 //   capi_exp.hip    experiment hooks (libbee2hip_exp.so only)
 #include "staging.hpp"
 static const bool g_capture_query_set = (bee2hip::g_stream_capturing = bee2hip::stream_is_capturing, true);
@@ -24,4 +25,5 @@ static const bool g_capture_query_set = (bee2hip::g_stream_capturing = bee2hip::
 #include "capi_mixed.hip"
 #include "capi_prg.hip"
 #include "capi_beltae.hip"
+#include "capi_fmt.hip"
 #include "capi_exp.hip"

@@ -70,6 +70,7 @@ DROPIN_SYMBOLS = [
     "beltCHEStepV", "beltCHEWrap", "beltCHEUnwrap",
     "beltMAC_keep", "beltMACStart", "beltMACStepA", "beltMACStepG", "beltMACStepG2",
     "beltMACStepV", "beltMACStepV2", "beltMAC",
+    "beltFMTEncr", "beltFMTDecr",
     "bignParamsStd", "bignVerify", "bign128Verify", "bign192Verify", "bign256Verify",
     "bignPubkeyVal", "bign128PubkeyVal", "bign192PubkeyVal", "bign256PubkeyVal",
     "bignKeypairGen", "bignPubkeyCalc", "bignSign", "bignSign2",
@@ -99,6 +100,7 @@ BATCH_SYMBOLS = [
     "bee2hip_bashPrgHash_ragged", "bee2hip_bashPrgAE_wrap_ragged", "bee2hip_bashPrgAE_unwrap_ragged",
     "bee2hip_bashPrgHash_ragged_stream", "bee2hip_bashPrgAE_ragged_stream",
     "bee2hip_beltAE_wrap_ragged", "bee2hip_beltAE_unwrap_ragged", "bee2hip_beltAE_ragged_stream",
+    "bee2hip_beltFMT_batch", "bee2hip_beltFMT_batch_stream",
     "bee2hip_set_device", "bee2hip_sync", "bee2hip_last_error", "bee2hip_version", "bee2hip_path_policy", "bee2hip_path_count",
 ]
 # include/bee2hip_internal.h: test / bench hooks, not product ABI
@@ -388,6 +390,13 @@ class Engine:
             self._optr(hdr_offsets), self._optr(src), self._ptr(offsets), self._optr(order), _sz(n), self._optr(dst),
             self._ptr(tags), self._optr(codes), self._stream()), "beltAE_ragged_stream")
 
+    def beltFMT_batch_stream(self, decr, mod, count, key, ivs, src, dst, n):
+        """belt-fmt over n records of `count` symbols (u16) modulo `mod`: ivs (u8, n*16, or None: all zero), src and dst (may be
+        src) are device tensors; key (bytes) is shared by the batch"""
+        self._check(self.lib.bee2hip_beltFMT_batch_stream(
+            ctypes.c_int(1 if decr else 0), _u32(mod), _sz(count), bytes(key), _sz(len(key)), self._optr(ivs), self._optr(src),
+            _sz(n), self._optr(dst), self._stream()), "beltFMT_batch_stream")
+
     def time_kernel(self, which, reps, a=None, b=None, c=None, d=None, n=0, aux=0):
         ms = ctypes.c_float(0)
         p = [self._ptr(t) if t is not None else None for t in (a, b, c, d)]
@@ -529,7 +538,24 @@ class Engine:
         """-> (code, [plaintext, zeros where refused], [ERR_OK / ERR_BAD_MAC per record])"""
         return self._belt_ae(True, mode, key, ivs, headers, texts, tags)
 
+    def beltFMT_batch(self, decr, mod, count, key, ivs, records):
+        """belt-fmt: records = n * count little-endian u16 (bytes), ivs = n * 16 octets or None -> (code, bytes)"""
+        n = len(records) // (2 * count)
+        assert len(records) == 2 * count * n and (ivs is None or len(ivs) == 16 * n)
+        dst = ctypes.create_string_buffer(max(1, len(records)))
+        code = self.lib.bee2hip_beltFMT_batch(ctypes.c_int(decr), _u32(mod), _sz(count), bytes(key), _sz(len(key)),
+                                              None if ivs is None else bytes(ivs), bytes(records), _sz(n), dst)
+        return code, dst.raw[:len(records)]
+
     # ------------------------------------------------- bee2 drop-in interface
+    def beltFMT(self, decr, mod, symbols, key, iv=None):
+        """beltFMTEncr / beltFMTDecr on a list of symbols -> (code, [symbols])"""
+        n = len(symbols)
+        src, dst = (ctypes.c_uint16 * max(n, 1))(*symbols), (ctypes.c_uint16 * max(n, 1))()
+        f = self.lib.beltFMTDecr if decr else self.lib.beltFMTEncr
+        code = f(dst, _u32(mod), src, _sz(n), bytes(key), _sz(len(key)), None if iv is None else bytes(iv))
+        return code, list(dst)[:n]
+
     def beltH(self):
         p = self.lib.beltH()
         return bytes(p[i] for i in range(256))

@@ -51,6 +51,7 @@ extern "C" {
 
 /* ---- bee2 base types (include/bee2/defs.h:269,441,463,520) ---------------- */
 typedef uint8_t octet;
+typedef uint16_t u16;
 typedef uint32_t u32;
 typedef int bool_t;
 typedef uint32_t err_t;
@@ -403,6 +404,30 @@ err_t bee2hip_beltAE_unwrap_ragged(int mode, const octet key[], size_t key_len, 
 err_t bee2hip_beltAE_ragged_stream(int unwrap, int mode, const octet key[], size_t key_len, const void *d_ivs,
                                    const void *d_hdrs, const void *d_hdr_offsets, const void *d_src, const void *d_offsets,
                                    const void *d_order, size_t n, void *d_dst, void *d_tags, void *d_codes, void *stream);
+
+/* ---- belt-fmt: format-preserving encryption of n records (STB 34.101.31; belt.h, src/crypto/belt/belt_fmt.c) ----------
+   A record is `count` symbols (u16) of the alphabet 0 .. mod - 1, 2 <= mod <= 65536, 2 <= count <= 600; the result is again
+   `count` symbols of that alphabet.  Every record of a batch has the same mod and count and the same key: record i is
+   src + i * count, its synchro value ivs + 16 i (ivs == NULL: every synchro value is 16 zero octets), its result
+   dst + i * count.  decr = 0 encrypts, 1 decrypts.  One lane of belt_fmt_batch_kernel per record.
+   Before any device work: ERR_BAD_INPUT unless decr is 0 or 1, 2 <= mod <= 65536, count >= 2, key_len is 16, 24 or 32, key
+   is not NULL and n < 2^32, or when src or dst is NULL with n > 0; ERR_NOT_IMPLEMENTED for count > 600, as bee2; n = 0 is
+   ERR_OK without a device.
+   Symbols are NOT validated, as in bee2, which only EXPECTs them to be below mod: a symbol >= mod is not refused, it enters
+   the arithmetic as it is -- the number of a half is the sum of symbol_j mod^j modulo 2^(64 b), and a symbol that receives a
+   digit becomes (symbol + digit) mod mod -- and the result is what bee2 computes for the same input. */
+err_t bee2hip_beltFMT_batch(int decr, u32 mod, size_t count, const octet key[], size_t key_len, const octet *ivs,
+                            const u16 *src, size_t n, u16 *dst);
+/* The same on device pointers, asynchronous on `stream` (one queue, no fork; may be captured into a graph).  key is a HOST
+   pointer: it is expanded on the host and travels in the launch arguments.  d_src and d_dst are 2-aligned, d_ivs needs no
+   alignment.  d_dst == d_src processes in place; any other overlap of the two ranges is ERR_BAD_INPUT with nothing written. */
+err_t bee2hip_beltFMT_batch_stream(int decr, u32 mod, size_t count, const octet key[], size_t key_len, const void *d_ivs,
+                                   const void *d_src, size_t n, void *d_dst, void *stream);
+/* bee2's one-shots (belt.h; codes as belt_fmt.c:422-476, ERR_BAD_INPUT when dest overlaps iv included).  One record is one
+   serial chain: it runs on the host path unless the path policy is 1, which runs the kernel with n = 1.
+   DIFFERENCE FROM bee2: a mod outside 2 .. 65536 is ERR_BAD_INPUT here; bee2 only asserts it. */
+err_t beltFMTEncr(u16 dest[], u32 mod, const u16 src[], size_t count, const octet key[], size_t len, const octet iv[16]);
+err_t beltFMTDecr(u16 dest[], u32 mod, const u16 src[], size_t count, const octet key[], size_t len, const octet iv[16]);
 
 /* ---- one host batch over several GPUs from one process --------------------------------
    The batch is cut into contiguous index ranges (bee2hip_multi_plan), one worker thread per device runs the

@@ -1,0 +1,222 @@
+"""CPU side of belt-fmt (format-preserving encryption, STB 34.101.31): the plain-Python model (tests/orc_beltfmt.py) against the
+reference's recorded outputs and the standard's vectors; every refusal of the C ABI without a device; the host path
+(bee2_amd/csrc/host_fmt.hpp) against the model through a g++ shim and once more as a stand-alone program under
+-fsanitize=address,undefined; the division step the kernel and the host path share, in compiled code; the block counts."""
+import ctypes
+import json
+import os
+import random
+import re
+import struct
+import subprocess
+
+import pytest
+
+import bee2_amd
+import beltfmtgrid as G
+import orc_beltfmt as M
+from bee2_amd import engine as E
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SHIM = os.path.join(ROOT, "tests", "hostshim")
+NAMES = ("bee2hip_beltFMT_batch", "bee2hip_beltFMT_batch_stream", "beltFMTEncr", "beltFMTDecr")
+_sz, _u32 = ctypes.c_size_t, ctypes.c_uint32
+
+
+@pytest.fixture(scope="module")
+def fixture():
+    return json.load(open(os.path.join(ROOT, "tests", "golden", "belt_fmt.json")))
+
+
+@pytest.fixture(scope="module")
+def want():
+    """the model's output for every (shape, direction) the host-path tests use, computed once: {(mod, count, decr): (case, out)}"""
+    out = {}
+    for j, (mod, count) in enumerate(G.ALL_SHAPES):
+        for decr in (0, 1):
+            c = {"mod": mod, "count": count, "key_len": G.KEY_LENS[(j + decr) % 3], "iv": (j + decr) % 4 != 0,
+                 "oor": (j + decr) % 2 == 1, "seed": 4242 + 2 * j + decr, "decr": decr}
+            x = G.case_inputs(c)
+            out[(mod, count, decr)] = (x, M.crypt(decr, mod, x["symbols"], x["key"], x["iv"]))
+    return out
+
+
+# ================================================================================================ the model
+def test_fixture_covers_every_shape_key_length_and_direction(fixture):
+    rows = fixture["rows"]
+    assert [{k: r[k] for k in ("mod", "count", "key_len", "decr", "iv", "oor", "seed")} for r in rows] == G.fixture_cases()
+    assert {(r["mod"], r["count"]) for r in rows} == set(G.ALL_SHAPES)
+    for shape in G.ALL_SHAPES:
+        mine = [r for r in rows if (r["mod"], r["count"]) == shape]
+        assert {(r["key_len"], r["decr"]) for r in mine} == {(k, d) for k in G.KEY_LENS for d in (0, 1)}
+    assert any(r["oor"] for r in rows) and any(not r["iv"] for r in rows)
+    assert os.path.getsize(os.path.join(ROOT, "tests", "golden", "belt_fmt.json")) < 300 * 1024
+
+
+def test_model_reproduces_every_fixture_row(fixture):
+    for r in fixture["rows"]:
+        x = G.case_inputs(r)
+        assert G.encode(M.crypt(r["decr"], r["mod"], x["symbols"], x["key"], x["iv"])) == r["out"], r
+
+
+def test_model_reproduces_the_published_vectors(golden):
+    key, iv = golden.H[128:160], golden.H[192:208]
+    for mod, out in G.BEE2_VECTORS:
+        src = list(range(len(out)))
+        assert M.crypt(0, mod, src, key, iv) == out
+        assert M.crypt(1, mod, out, key, iv) == src
+
+
+def test_block_counts_equal_the_recorded_ones_the_exception_included(fixture):
+    blocks = fixture["blocks"]
+    assert [49667, 160, 40] in blocks and [49667, 159, 39] in blocks and len(blocks) >= 300
+    assert [[m, n] for m, n, _ in blocks] == [list(p) for p in G.block_pairs()]
+    for m, n, b in blocks:
+        assert M.block_count(m, n) == b, (m, n)
+    for r in fixture["rows"]:
+        assert G.blocks(r["mod"], r["count"]) == (r["b1"], r["b2"])
+    assert max(max(r["b1"], r["b2"]) for r in fixture["rows"]) == 75
+    # the exact value at the exception is 39: the 40 is the reference's approximation, and part of the cipher
+    assert -(-(49667 ** 160 - 1).bit_length() // 64) == 39
+
+
+@pytest.mark.ref
+def test_model_equals_the_live_reference_on_a_fresh_seed():
+    import refgen
+    if not refgen.have_ref():
+        pytest.skip("oracle/_ref not built")
+    L = refgen.ref()
+    rnd = random.Random(int.from_bytes(os.urandom(4), "little"))
+    for mod, count in G.ALL_SHAPES:
+        for decr in (0, 1):
+            key, iv = rnd.randbytes(rnd.choice(G.KEY_LENS)), rnd.choice((None, rnd.randbytes(16)))
+            syms = G.symbols(rnd, mod, count, rnd.random() < 0.3)
+            src, dst = (ctypes.c_uint16 * count)(*syms), (ctypes.c_uint16 * count)()
+            code = (L.beltFMTDecr if decr else L.beltFMTEncr)(dst, _u32(mod), src, _sz(count), key, _sz(len(key)), iv)
+            assert code == 0 and list(dst) == M.crypt(decr, mod, syms, key, iv), (mod, count, decr, syms, key, iv)
+
+
+# ================================================================================================ the interface
+def test_header_exports_and_engine_list_the_four_names():
+    header = open(os.path.join(ROOT, "include", "bee2hip.h")).read()
+    exported = E.lib_exports()
+    for name in NAMES:
+        assert re.search(r"\b%s\(" % name, header), name
+        assert name in exported, name
+        assert name in (E.BATCH_SYMBOLS if name.startswith("bee2hip_") else E.DROPIN_SYMBOLS), name
+    assert {"beltFMT_batch", "beltFMT_batch_stream", "beltFMT"} <= set(dir(E.Engine))
+
+
+def test_every_refusal_answers_without_a_device():
+    """(this machine may have no GPU at all: an entry that reached for the device would answer ERR_BEE2HIP_DEVICE)"""
+    lib = bee2_amd.load().lib
+    key, rec = bytes(32), (ctypes.c_uint16 * 1300)()
+    fake = ctypes.c_void_p(0x10000)                        # never dereferenced: every call below is refused first
+
+    def batch(decr=0, mod=10, count=16, key=key, key_len=32, n=1, src=rec, dst=rec):
+        return lib.bee2hip_beltFMT_batch(ctypes.c_int(decr), _u32(mod), _sz(count), key, _sz(key_len), None, src, _sz(n), dst)
+
+    def stream(decr=0, mod=10, count=16, key=key, key_len=32, n=1, src=fake, dst=fake):
+        return lib.bee2hip_beltFMT_batch_stream(ctypes.c_int(decr), _u32(mod), _sz(count), key, _sz(key_len), None, src, _sz(n),
+                                                dst, None)
+
+    for f in (batch, stream):
+        assert f(decr=2) == E.ERR_BAD_INPUT and f(decr=-1) == E.ERR_BAD_INPUT
+        assert f(mod=0) == f(mod=1) == f(mod=65537) == E.ERR_BAD_INPUT
+        assert f(count=0) == f(count=1) == E.ERR_BAD_INPUT
+        assert f(key_len=0) == f(key_len=17) == f(key_len=33) == E.ERR_BAD_INPUT
+        assert f(key=None) == E.ERR_BAD_INPUT
+        assert f(n=1 << 32) == E.ERR_BAD_INPUT
+        assert f(count=601) == E.ERR_NOT_IMPLEMENTED and f(count=601, n=0) == E.ERR_NOT_IMPLEMENTED
+        assert f(count=601, mod=1) == E.ERR_BAD_INPUT          # bad input before not implemented, as bee2
+        assert f(src=None) == f(dst=None) == E.ERR_BAD_INPUT
+        assert f(n=0) == f(n=0, src=None, dst=None) == E.ERR_OK
+        assert f(n=0, count=600, mod=65536) == E.ERR_OK
+    # the stream entry: alignment 2, and any overlap other than dst == src
+    assert stream(src=ctypes.c_void_p(0x10001)) == stream(dst=ctypes.c_void_p(0x10001)) == E.ERR_BAD_INPUT
+    assert stream(n=4, src=ctypes.c_void_p(0x10000), dst=ctypes.c_void_p(0x10000 + 2 * 16 * 4 - 2)) == E.ERR_BAD_INPUT
+    assert stream(n=4, src=ctypes.c_void_p(0x10000 + 2), dst=ctypes.c_void_p(0x10000)) == E.ERR_BAD_INPUT
+    # the one-shots (belt_fmt.c:427-436, and the mod range bee2 only asserts)
+    src, dst, iv = (ctypes.c_uint16 * 700)(), (ctypes.c_uint16 * 700)(), bytes(16)
+    for f in (lib.beltFMTEncr, lib.beltFMTDecr):
+        def one(dest=dst, mod=10, s=src, count=16, key=key, key_len=32, iv=iv):
+            return f(dest, _u32(mod), s, _sz(count), key, _sz(key_len), iv)
+        assert one(count=1) == one(count=0) == E.ERR_BAD_INPUT
+        assert one(key_len=20) == one(key=None) == one(s=None) == one(dest=None) == E.ERR_BAD_INPUT
+        assert one(mod=1) == one(mod=65537) == one(mod=0) == E.ERR_BAD_INPUT
+        assert one(count=601) == E.ERR_NOT_IMPLEMENTED
+        assert one(count=601, key_len=20) == E.ERR_BAD_INPUT
+        # dest overlapping iv (belt_fmt.c:433): the iv inside dest, at its end, and dest inside the iv
+        raw = (ctypes.c_ubyte * 128)()
+        base = ctypes.addressof(raw)
+        d = ctypes.cast(base + 32, ctypes.POINTER(ctypes.c_uint16))
+        for iv_at in (base + 32, base + 32 + 31, base + 17, base + 40):
+            assert one(dest=d, iv=ctypes.c_void_p(iv_at)) == E.ERR_BAD_INPUT, iv_at - base
+
+
+# ================================================================================================ the host path
+@pytest.fixture(scope="module")
+def hf(tmp_path_factory, golden):
+    out = tmp_path_factory.mktemp("hostfmt") / "libhostfmt.so"
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wextra", "-Werror", "-o", str(out),
+                           os.path.join(SHIM, "host_fmt_shim.cpp")])
+    lib = ctypes.CDLL(str(out))
+    lib.hf_block_count.restype = _sz
+    for name in ("hf_div_exhaustive", "hf_div_sampled", "hf_divmod_small"):
+        getattr(lib, name).restype = ctypes.c_uint64
+    lib.hf_init(golden.H)
+    return lib
+
+
+def test_host_path_equals_the_model_on_every_shape_and_direction(hf, orc, want):
+    assert any(any(s >= mod for s in x["symbols"]) for (mod, _, _), (x, _) in want.items())
+    for (mod, count, decr), (x, out) in want.items():
+        buf = (ctypes.c_uint16 * count)(*x["symbols"])
+        hf.hf_crypt(decr, _u32(mod), _sz(count), orc.key_expand(x["key"]), x["iv"], buf)
+        assert list(buf) == out, (mod, count, decr)
+    key, iv = bytes(range(32)), bytes(range(16))
+    for mod, vec in G.BEE2_VECTORS:                                      # and a round trip of in-range records
+        buf = (ctypes.c_uint16 * len(vec))(*vec)
+        hf.hf_crypt(0, _u32(mod), _sz(len(vec)), orc.key_expand(key), iv, buf)
+        assert list(buf) != vec
+        hf.hf_crypt(1, _u32(mod), _sz(len(vec)), orc.key_expand(key), iv, buf)
+        assert list(buf) == vec
+
+
+def test_host_path_as_a_program_of_its_own_under_asan_and_ubsan(tmp_path, golden, orc, want):
+    """the same cases through tests/hostshim/host_fmt_san_main.cpp, compiled -fsanitize=address,undefined and run as a
+    subprocess: every record buffer is exactly the record, so a read or write past it ends the program"""
+    exe = tmp_path / "host_fmt_san"
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-static-libasan", "-o", str(exe), os.path.join(SHIM, "host_fmt_san_main.cpp")])
+    lines, outs = [golden.H.hex()], []
+    for (mod, count, decr), (x, out) in want.items():
+        kw = " ".join(f"{w:x}" for w in orc.key_expand(x["key"]))
+        lines.append(f"{decr} {mod} {count} {kw} {x['iv'].hex() if x['iv'] else '-'} " + " ".join(map(str, x["symbols"])))
+        outs.append(out)
+    path = tmp_path / "cases.txt"
+    path.write_text("\n".join(lines) + "\n")
+    res = subprocess.run([str(exe), str(path)], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr[-2000:]
+    got = [[int(v) for v in line.split()] for line in res.stdout.splitlines()]
+    assert got == outs
+
+
+def test_block_count_of_the_library_code(hf, fixture):
+    for m, n, b in fixture["blocks"]:
+        assert hf.hf_block_count(_u32(m), _sz(n)) == b, (m, n)
+
+
+# ================================================================================================ the division step
+@pytest.mark.parametrize("mod", [2, 3, 10, 58, 255, 256, 257])
+def test_division_step_is_exact_for_every_remainder_and_piece(hf, mod):
+    assert hf.hf_div_exhaustive(_u32(mod)) == 0
+    assert hf.hf_divmod_small(_u32(mod)) == 0
+
+
+@pytest.mark.parametrize("mod", [32767, 32768, 32769, 49667, 65521, 65535, 65536])
+def test_division_step_is_exact_at_the_edges_and_on_seeded_remainders(hf, mod):
+    """every h with rem in {0, 1, mod / 2, mod - 2, mod - 1} and 1024 seeded remainders; 65536 is beyond what the issue asks:
+    the general path must also hold for the modulus the kernel serves by shifts"""
+    assert hf.hf_div_sampled(_u32(mod), _u32(1024), ctypes.c_uint64(0xD1F + mod)) == 0
+    assert hf.hf_divmod_small(_u32(mod)) == 0
