@@ -149,6 +149,7 @@ def _triples(l):
 
 
 _generic = None
+_generic_adv = None
 
 
 def f_verify_generic(rnd):
@@ -386,16 +387,26 @@ def f_sign_generic(rnd):
     """round 3: the signing side on a non-standard parameter set (isomorphic images of the standard curves: q is the group
     order).  Checker: the Python restatement of bignVerify (tests/orc_generic.py) must accept every signature the library
     makes, the library must verify them itself, and the public key must come out of bignPubkeyVal as valid; refused private
-    keys keep their codes.  Long OIDs (up to ~600 octets) ride along on this family and on the standard curves (oracle)."""
-    global _generic
+    keys keep their codes, and every signature equals the Python restatement of bignSign2 (tests/orc_sign2.py: the one-time key of
+    algorithm 6.3.3, then orc_generic.sign_k).  Every other case runs on an ADVERSARIAL set instead (tests/golden/bign_generic_adv.json:
+    q = 2^(2l-1) + 1, "low limb 1", "random odd"), where the one-time-key loop rejects up to one draw in two and the lanes of a
+    batch leave it at different passes: q is not the group order there, so nothing verifies, and the checker is the model alone --
+    the k recovered from each signature is the model's, and one signature per case equals the model's in full.
+    Long OIDs (up to ~600 octets) ride along on this family and on the standard curves (oracle)."""
+    global _generic, _generic_adv
     import json
     import orc_generic as OG
+    import orc_sign2 as S2
     from bee2_amd import engine as E
     from bee2_amd.engine import bign_params
     if _generic is None:
         _generic = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bign_generic.json")))
+    if _generic_adv is None:
+        _generic_adv = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bign_generic_adv.json")))
     iso = [i for i, c in enumerate(_generic["curves"]) if c["kind"] == "iso" and c["l"] <= 192]
-    c = _generic["curves"][rnd.choice(iso)]
+    rejecting = [c for c in _generic_adv["sets"] if c["kind"] == "adv" and c["q_kind"] in ("2^(2l-1) + 1", "low limb 1", "random odd")]
+    adv = rnd.randrange(2) == 1
+    c = rnd.choice(rejecting) if adv else _generic["curves"][rnd.choice(iso)]
     prm = bign_params()
     prm.l = c["l"]
     for f in ("p", "a", "b", "q", "yG"):
@@ -411,7 +422,7 @@ def f_sign_generic(rnd):
         total, hdr, body = 11, 2, 9
     oid = (bytes([0x06, body]) if hdr == 2 else bytes([0x06, 0x81, body]) if hdr == 3 else bytes([0x06, 0x82, body >> 8, body & 255])) + \
         bytes([0x2A] + [rnd.randrange(1, 128) for _ in range(body - 1)])
-    n = rnd.randrange(1, 6)
+    n = rnd.choice((1, 3, 64, 65, 130)) if adv else rnd.randrange(1, 6)
     privs = [rnd.randrange(1, q).to_bytes(no, "little") for _ in range(n)]
     bad = rnd.randrange(n) if rnd.randrange(3) == 0 else -1
     if bad >= 0:
@@ -428,6 +439,15 @@ def f_sign_generic(rnd):
                 return False
             continue
         if sc[i] != 0:
+            return False
+        if adv:
+            k, _ = S2.nonce(oid, privs[i], t, hs[i], q, orc.belt_hash, orc.wbl)
+            if S2.recover_k(l, q, sigs[sg * i: sg * (i + 1)], privs[i], hs[i]) != k:
+                return False
+            if i == (bad + 1) % n and OG.sign_k(P, oid, hs[i], privs[i], k.to_bytes(no, "little"), orc.belt_hash) != (0, sigs[sg * i: sg * (i + 1)]):
+                return False
+            continue
+        if S2.sign2(P, oid, hs[i], privs[i], t, orc.belt_hash, orc.wbl) != (0, sigs[sg * i: sg * (i + 1)]):
             return False
         pc, pub = eng.bignPubkeyCalc(prm, privs[i])
         s_i = sigs[sg * i: sg * (i + 1)]

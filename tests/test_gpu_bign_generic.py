@@ -9,6 +9,7 @@ import random
 import pytest
 
 import orc_generic as OG
+import orc_sign2 as S2
 from bee2_amd.engine import bign_params
 from gpulib import engine
 
@@ -301,8 +302,9 @@ def test_generic_batches_at_wavefront_boundaries(orc, l):
     """one lane per item, 64 lanes per block: n = 1, 63, 64, 65, 1000 through every generic batch entry, refused items
     (early-return lanes: a coordinate >= p, s1 >= q, d = 0, d >= q, k = q) next to working ones in every wavefront, every
     output compared item by item; refused items leave zeros.  The expected values of the distinct items come from
-    orc_generic; the deterministic signatures of bignSign2 (no Python restatement of their one-time key) must be equal
-    for equal inputs, verify under orc_generic.verify, and be refused exactly where the key is out of range."""
+    orc_generic; the deterministic signatures of bignSign2 must be equal for equal inputs, verify under orc_generic.verify, be
+    refused exactly where the key is out of range, and equal orc_sign2.sign2 (the Python restatement of their one-time key; q is
+    the standard one here, so its loop makes one pass -- tests/test_gpu_bign_sign2_loop.py has the q's that make more)."""
     eng = engine()
     si, s = [(i, x) for i, x in enumerate(AFIX["sets"]) if x["l"] == l and x["kind"] == "iso"][0]
     prm, P = mk(s), OG.Params.from_hex(s)
@@ -354,3 +356,4 @@ def test_generic_batches_at_wavefront_boundaries(orc, l):
     assert sorted(s2ref) == [i for i, d in enumerate(dpool) if 0 < d < q]
     for i, one in s2ref.items():
         assert OG.verify(P, oid, hpool[i], one, pcwant[i][1], orc.belt_hash) == 0, i
+        assert S2.sign2(P, oid, hpool[i], enc(dpool[i]), None, orc.belt_hash, orc.wbl) == (0, one), i
