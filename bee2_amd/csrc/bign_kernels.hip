@@ -53,6 +53,7 @@
 #include "bign_fe29.hpp"
 #include "bign_quad29.hpp"
 #include "common.hpp"
+#include "bign_keytab.hpp"         // the one-signer table cache; device_table_once
 #include "host_bign.hpp"          // host arithmetic of the one-signer path: the points 2^(8 w) Q (verification: no secrets)
 #include "bign_curves.inc"
 
@@ -1494,35 +1495,30 @@ __global__ void bign_debug_fe_kernel(int op, const uint32_t *a, const uint32_t *
 #endif   // BEE2HIP_EXPERIMENTS
 
 // ------------------------------------------------------------------ host side ---
-struct BignDevice {
-    uint4 *gtab8[3] = {nullptr, nullptr, nullptr};     // 8-bit seed table per curve (index N/4 - 2): 4N x 256 affine points
-    uint4 *gtab[3] = {nullptr, nullptr, nullptr};      // 16-bit comb table per curve, built from the seed table
-    uint4 *gtab6[3] = {nullptr, nullptr, nullptr};     // signed 6-bit windows (signing side, one lane per scalar)
-    uint4 *gtabw8[3] = {nullptr, nullptr, nullptr};    // signed 8-bit windows (signing side, LDS look-up kernel: 256-bit curve)
-};
+enum { GTAB8, GTAB16, GTAB6, GTABW8 };
+struct BignDevice {                   // G's tables per curve (index N/4 - 2), each made once:
+    uint4 *tab[4][3] = {};            //   GTAB8  8-bit seed table: 4N x 256 affine points
+};                                    //   GTAB16 16-bit comb table, built from the seed table
+                                      //   GTAB6  signed 6-bit windows (signing side, one lane per scalar)
+                                      //   GTABW8 signed 8-bit windows (signing side, LDS look-up kernel: 256-bit curve)
 static BignDevice g_bign[64];
 static std::mutex g_bign_mu;          // table construction is per device, shared by threads
 
-// the seed table alone (0.5 / 1.7 / 4 MiB): all the signing / key generation path needs (bign_sign_kernels.hip).
-// Caller holds g_bign_mu.
+// the seed table alone (0.5 / 1.7 / 4 MiB): all the signing / key generation path needs (bign_sign_kernels.hip); *tabs = the
+// calling thread's device's tables.  Caller holds g_bign_mu.
 template <int N>
-static err_t bign_table8_locked(uint4 **out, hipStream_t st)
+static err_t bign_table8_locked(uint4 **out, hipStream_t st, BignDevice **tabs = nullptr)
 {
     int dev = 0;
     B2H_TRY(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64) return ERR_BAD_INPUT;
-    uint4 *&slot = g_bign[dev].gtab8[N / 4 - 2];
-    if (!slot) {
-        const size_t pt = 8 * N;                                      // bytes per affine point
-        uint4 *t8 = nullptr;
-        if (hipMalloc((void **)&t8, (size_t)4 * N * GT8_ENTRIES * pt) != hipSuccess) { (void)hipGetLastError(); return ERR_OUTOFMEMORY; }
+    if (tabs) *tabs = &g_bign[dev];
+    const size_t pt = 8 * N;                                          // bytes per affine point
+    const err_t code = device_table_once(&g_bign[dev].tab[GTAB8][N / 4 - 2], (size_t)4 * N * GT8_ENTRIES * pt, st, [&](uint4 *t8) {
         hipLaunchKernelGGL(bign_gtable_kernel<N>, dim3(4 * N * GT8_ENTRIES / 64), dim3(64), 0, st, t8);
-        B2H_TRY(hipGetLastError());
-        B2H_TRY(hipStreamSynchronize(st));
-        slot = t8;
-    }
-    *out = slot;
-    return ERR_OK;
+    });
+    *out = g_bign[dev].tab[GTAB8][N / 4 - 2];
+    return code;
 }
 template <int N>
 static err_t bign_table8(const uint32_t **out, hipStream_t st)
@@ -1534,29 +1530,30 @@ static err_t bign_table8(const uint32_t **out, hipStream_t st)
     return code;
 }
 
+// the seed table, and table `which` of `entries` points made from it by `kern` in blocks of wg.  Caller holds g_bign_mu.
+template <int N, class Kernel>
+static err_t bign_table_from8(int which, size_t entries, unsigned wg, Kernel kern, uint4 **out8, uint4 **out, hipStream_t st)
+{
+    BignDevice *d = nullptr;
+    err_t code = bign_table8_locked<N>(out8, st, &d);
+    if (code != ERR_OK) return code;
+    code = device_table_once(&d->tab[which][N / 4 - 2], entries * 8 * N, st, [&](uint4 *t) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)((entries + wg - 1) / wg)), dim3(wg), 0, st, (const uint4 *)*out8, t);
+    });
+    *out = d->tab[which][N / 4 - 2];
+    return code;
+}
+
 // seed table and the signed 6-bit table made from it (88 / 200 / 352 KiB)
 template <int N>
 static err_t bign_table6(const uint32_t **out8, const uint32_t **out6, hipStream_t st)
 {
     std::lock_guard<std::mutex> lk(g_bign_mu);
-    uint4 *t8 = nullptr;
-    err_t code = bign_table8_locked<N>(&t8, st);
-    if (code != ERR_OK) return code;
-    int dev = 0;
-    B2H_TRY(hipGetDevice(&dev));
-    uint4 *&slot = g_bign[dev].gtab6[N / 4 - 2];
-    if (!slot) {
-        uint4 *t6 = nullptr;
-        const size_t entries = (size_t)Win6<N>::W * 32;
-        if (hipMalloc((void **)&t6, entries * 8 * N) != hipSuccess) { (void)hipGetLastError(); return ERR_OUTOFMEMORY; }
-        hipLaunchKernelGGL(bign_gtable6_kernel<N>, dim3((unsigned)((entries + 63) / 64)), dim3(64), 0, st, (const uint4 *)t8, t6);
-        B2H_TRY(hipGetLastError());
-        B2H_TRY(hipStreamSynchronize(st));
-        slot = t6;
-    }
+    uint4 *t8 = nullptr, *t6 = nullptr;
+    const err_t code = bign_table_from8<N>(GTAB6, (size_t)Win6<N>::W * 32, 64, bign_gtable6_kernel<N>, &t8, &t6, st);
     *out8 = reinterpret_cast<const uint32_t *>(t8);
-    *out6 = reinterpret_cast<const uint32_t *>(slot);
-    return ERR_OK;
+    *out6 = reinterpret_cast<const uint32_t *>(t6);
+    return code;
 }
 
 // the signed 8-bit window table (264 KiB on the 256-bit curve), made from the seed table like the 6-bit one
@@ -1565,46 +1562,18 @@ static err_t bign_tablew(const uint32_t **outw, hipStream_t st)
 {
     static_assert(WB == 8, "window table of the LDS look-up kernel");
     std::lock_guard<std::mutex> lk(g_bign_mu);
-    uint4 *t8 = nullptr;
-    err_t code = bign_table8_locked<N>(&t8, st);
-    if (code != ERR_OK) return code;
-    int dev = 0;
-    B2H_TRY(hipGetDevice(&dev));
-    uint4 *&slot = g_bign[dev].gtabw8[N / 4 - 2];
-    if (!slot) {
-        uint4 *tw = nullptr;
-        const size_t entries = (size_t)WinW<N, WB>::W * WinW<N, WB>::ENT;
-        if (hipMalloc((void **)&tw, entries * 8 * N) != hipSuccess) { (void)hipGetLastError(); return ERR_OUTOFMEMORY; }
-        hipLaunchKernelGGL((bign_gtable6_kernel<N, WB>), dim3((unsigned)((entries + 63) / 64)), dim3(64), 0, st, (const uint4 *)t8, tw);
-        B2H_TRY(hipGetLastError());
-        B2H_TRY(hipStreamSynchronize(st));
-        slot = tw;
-    }
-    *outw = reinterpret_cast<const uint32_t *>(slot);
-    return ERR_OK;
+    uint4 *t8 = nullptr, *tw = nullptr;
+    const err_t code = bign_table_from8<N>(GTABW8, (size_t)WinW<N, WB>::W * WinW<N, WB>::ENT, 64, bign_gtable6_kernel<N, WB>, &t8, &tw, st);
+    *outw = reinterpret_cast<const uint32_t *>(tw);
+    return code;
 }
 
+// the 16-bit comb table of general verification.  Caller holds g_bign_mu.
 template <int N>
 static err_t bign_table(uint4 **out, hipStream_t st)
 {
-    int dev = 0;
-    B2H_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return ERR_BAD_INPUT;
-    uint4 *&slot = g_bign[dev].gtab[N / 4 - 2];
-    if (!slot) {
-        const size_t pt = 8 * N;
-        uint4 *t8 = nullptr;
-        const err_t code = bign_table8_locked<N>(&t8, st);
-        if (code != ERR_OK) return code;
-        uint4 *t16 = nullptr;
-        if (hipMalloc((void **)&t16, (size_t)2 * N * 65536 * pt) != hipSuccess) { (void)hipGetLastError(); return ERR_OUTOFMEMORY; }
-        hipLaunchKernelGGL(bign_gtable16_kernel<N>, dim3(2 * N * 65536 / 256), dim3(256), 0, st, (const uint4 *)t8, t16);
-        B2H_TRY(hipGetLastError());
-        B2H_TRY(hipStreamSynchronize(st));
-        slot = t16;
-    }
-    *out = slot;
-    return ERR_OK;
+    uint4 *t8 = nullptr;
+    return bign_table_from8<N>(GTAB16, (size_t)2 * N * 65536, 256, bign_gtable16_kernel<N>, &t8, out, st);
 }
 
 template <int N>
@@ -1763,7 +1732,7 @@ err_t launch_bign_verify(size_t l, const uint8_t *oid_der, size_t oid_len, const
 // Is Q a point of the curve, and the 2N + 1 points 2^(8 w) Q the table kernel starts from: a chain of l doublings, ~25 us on a
 // host core (0.5 ms for a lone wavefront), made affine with one inversion.  NL = 64-bit limbs (N = 2 NL).
 template <int NL>
-static bool onekey_base_t(uint64_t crandall_c, const uint8_t *b_le, const uint8_t *pubkey, std::vector<uint8_t> &base)
+static bool onekey_base_t(uint64_t crandall_c, const uint8_t *b_le, const uint8_t *pubkey, uint8_t *base)
 {
     hostb::Curve<NL> E;                                 // (group law and field only: its tables of G are not needed)
     E.F.c = crandall_c;
@@ -1786,7 +1755,6 @@ static bool onekey_base_t(uint64_t crandall_c, const uint8_t *b_le, const uint8_
     if (hostb::Field<NL>::is_zero(acc)) return false;
     hostb::Fe<NL> inv;
     F.inv(inv, acc);
-    base.resize((size_t)W * 16 * NL);
     for (int w = W - 1; w >= 0; --w) {
         hostb::Fe<NL> zi, zi2, x, y;
         if (w) { F.mul(zi, inv, pre[w - 1]); F.mul(inv, inv, P[w].Z); } else zi = inv;
@@ -1794,13 +1762,13 @@ static bool onekey_base_t(uint64_t crandall_c, const uint8_t *b_le, const uint8_
         F.mul(x, P[w].X, zi2);
         F.mul(zi2, zi2, zi);
         F.mul(y, P[w].Y, zi2);
-        uint8_t *o = base.data() + (size_t)w * 16 * NL;
+        uint8_t *o = base + (size_t)w * 16 * NL;
         for (int i = 0; i < NL; ++i) { hostp::st64le(o + 8 * i, x.v[i]); hostp::st64le(o + 8 * NL + 8 * i, y.v[i]); }
     }
     return true;
 }
 template <int N>
-static bool onekey_base(const uint8_t *pubkey, std::vector<uint8_t> &base)
+static bool onekey_base(const uint8_t *pubkey, uint8_t *base)
 {
     if (N == 8) return onekey_base_t<4>(BIGN128_CRANDALL_C, k_bign128_b, pubkey, base);
     if (N == 12) return onekey_base_t<6>(BIGN192_CRANDALL_C, k_bign192_b, pubkey, base);
@@ -1808,239 +1776,37 @@ static bool onekey_base(const uint8_t *pubkey, std::vector<uint8_t> &base)
 }
 
 // ---- one signer: table cache and launcher --------------------------------------------------------------------------
-// The comb table of a public key lives in device memory, keyed by (device, curve, key octets); the last KEYTAB_SLOTS keys per
-// process are kept (a table is 278 KiB .. 1 MiB: the card holds as many as anybody wants, the limit only bounds the scan).
-// A launcher holds a reference while it queues its kernels; the table is freed when the last reference goes, and hipFree
-// waits for the device, so a kernel already queued never loses its table.
-// (round 5) A slab holds at most KEYSLAB_KEYS tables, so ONE busy key pins at most that many (4.4 - 16 MiB), and the
-// cache is bounded in BYTES as well (KEYTAB_BYTES_MAX of live slabs): before a new slab is allocated the least recently used
-// entries go until there is room, and when hipMalloc still refuses, every entry nobody holds goes and the allocation is tried
-// once more.  Keys that end up without a table are verified by the paths that need none (one signer: the general pipeline;
-// several: the complete-formula kernel) -- slower, same verdicts, no error.
-constexpr size_t KEYSLAB_KEYS = 16;
-constexpr size_t KEYTAB_BYTES_MAX = (size_t)8 << 30;
-static std::atomic<size_t> g_keyslab_bytes{0};
-struct KeySlab {                       // tables of keys one call met for the first time, in one device allocation
-    void *p = nullptr;
-    size_t bytes = 0;
-    ~KeySlab() { if (p) { (void)hipFree(p); g_keyslab_bytes.fetch_sub(bytes); } }
-};
-struct KeyTab {
-    std::shared_ptr<KeySlab> slab;     // (freed with the last of its tables)
-    const uint4 *tab = nullptr;        // (2N + 1) x 256 affine points
-    const uint8_t *d_key = nullptr;    // the key itself in device memory (2 NO octets)
-    uint4 *tab16 = nullptr;            // N x 65536 affine points (32 / 72 / 128 MiB): once `used` says the key is a busy one
-    uint64_t stamp = 0, used = 0;      // signatures verified under the key so far
-    ~KeyTab();
-};
-// at most KEYTAB16_MAX keys hold a 16-bit table at a time (<= 3 / 7 / 12 GiB per process): a key that becomes busy while they are
-// all taken stays on its 8-bit table
-constexpr int KEYTAB16_MAX = 96;
-static std::atomic<int> g_keytab16_live{0};
-unsigned long long bign_onekey_tab16_live() { return (unsigned long long)g_keytab16_live.load(); }
-KeyTab::~KeyTab() { if (tab16) { (void)hipFree(tab16); g_keytab16_live.fetch_sub(1); } }
-static size_t KEYTAB_SLOTS = 1024;                   // (0.3 - 1 GiB of 8-bit tables when full; tests: tune 21)
-void set_onekey_slots(int v) { KEYTAB_SLOTS = v < 1 ? 1 : (size_t)v; }
-static std::unordered_map<std::string, std::shared_ptr<KeyTab>> &g_keytabs = *new std::unordered_map<std::string, std::shared_ptr<KeyTab>>;   // (never destroyed: no hipFree behind the runtime's back at exit)
-// (round 5) the key-table cache has a lock of its own: building a key's tables (host arithmetic, a kernel, a synchronise:
-// 0.2-2 ms) holds it, and general verification -- which takes g_bign_mu to fetch G's table -- no longer waits behind that.  Never nested
-// with g_bign_mu.
-static std::mutex g_keytab_mu;
-static uint64_t g_keytab_clock = 0;
-static std::atomic<unsigned long long> g_keytab_builds{0};
-unsigned long long bign_onekey_table_builds() { return g_keytab_builds.load(); }
-
-// A key under which KEYTAB16_AFTER signatures have been verified gets the 16-bit table as well (0.3 / 1 / 2 ms to build -- the work
-// of ~2^17 signatures -- against a quarter of the additions saved from then on): made from the 8-bit one like G's (bign_gtable16_kernel).
+// The cache itself -- policy, locking, the order of work -- is bign_keytab.hpp; here are the curve's steps.
+static KeyTabCache &g_keytab = *new KeyTabCache;     // (never destroyed: no hipFree behind the runtime's back at exit)
+unsigned long long bign_onekey_tab16_live() { return (unsigned long long)g_keytab.n.tab16_live.load(); }
+unsigned long long bign_onekey_table_builds() { return g_keytab.n.builds.load(); }
+void set_onekey_slots(int v) { g_keytab.slots = v < 1 ? 1 : (size_t)v; }
+void set_onekey_tab16(int v) { g_keytab.tab16_log2 = v; }
 static int g_onekey_quads = -1;                      // four lanes per signature: -1 by batch size (<= 2^16), 0 never, 1 always (tests / A/B: tune 22)
 void set_onekey_quads(int v) { g_onekey_quads = v; }
-static int g_keytab16_log2 = -1;                     // -1: by curve (2^19 on the 256-bit curve, 2^20 on the wider ones); tests / A/B: tune 20
-void set_onekey_tab16(int v) { g_keytab16_log2 = v; }
-template <int N>
-static err_t bign_key_table16_locked(KeyTab &k, hipStream_t st)
-{
-    const size_t pt = 8 * N;
-    uint4 *t16 = nullptr;
-    if (g_keytab16_live.load() >= KEYTAB16_MAX) return ERR_OK;                                                        // enough busy keys already
-    if (hipMalloc((void **)&t16, (size_t)N * 65536 * pt) != hipSuccess) { (void)hipGetLastError(); return ERR_OK; }   // no room: the 8-bit table serves
-    hipLaunchKernelGGL(bign_gtable16_kernel<N>, dim3(N * 65536 / 256), dim3(256), 0, st, k.tab, t16);
-    hipError_t e16 = hipGetLastError();
-    if (e16 == hipSuccess) e16 = hipStreamSynchronize(st);
-    if (e16 != hipSuccess) { (void)hipFree(t16); return hip_fail(e16, "bign_gtable16_kernel (key)"); }
-    k.tab16 = t16;
-    g_keytab16_live.fetch_add(1);
-    return ERR_OK;
-}
 
-// The tables of nkeys keys (host memory, 2 NO octets each): out[k] = the cached entry, or null for a key that is not a point of
-// the curve.  The keys this process has not met (or has dropped) are built TOGETHER: their starting points on host threads (~35 us
-// a key), one allocation [tables | key, starting points per key], one upload, one launch of bign_ktable_kernel (0.17 ms for one key,
-// ~0.3 ms for 64: lone wavefronts fill the chip), one synchronisation.  n = signatures of this call (counted towards the 16-bit
-// table of a key when want16).
+// The tables of nkeys keys (host memory, 2 NO octets each): out[k] = the cached entry, or null for a key without one.
+// n = signatures of this call under each key (counted towards the 16-bit table of a key when want16).
 template <int N>
-static err_t bign_key_tables(std::vector<std::shared_ptr<KeyTab>> &out, const uint8_t *keys, size_t nkeys, size_t n, bool want16,
-                             hipStream_t st)
+static err_t bign_key_tables(KeyTabCache::Tabs &out, const uint8_t *keys, size_t nkeys, size_t n, bool want16, hipStream_t st)
 {
     constexpr size_t NO = 4 * N, pt = 8 * N;
     constexpr size_t TAB = (size_t)(2 * N + 1) * GT8_ENTRIES * pt, AUX = 2 * NO + (size_t)(2 * N + 1) * pt;     // table; key + starting points
     int dev = 0;
     B2H_TRY(hipGetDevice(&dev));
-    const int lg = g_keytab16_log2 >= 0 ? g_keytab16_log2 : N == 8 ? 19 : 20;
-    const uint64_t after = lg >= 63 ? ~(uint64_t)0 : (uint64_t)1 << lg;
-    out.assign(nkeys, nullptr);
-    // On a stream that is being captured only queued work is legal.  The 16-bit table of a busy key costs an allocation, a launch
-    // and a synchronisation, so a captured call never promotes a key -- it runs on the tables the key has -- and does not count
-    // towards the promotion either (a capture queues nothing: the replays verify, and the library does not see them).  The next
-    // eager call under the key promotes it as usual.
-    const bool capturing = stream_is_capturing(st);
-    if (capturing) want16 = false;
-    const auto id_of = [&](const uint8_t *key) {
-        std::string id(2 + 2 * NO, '\0');
-        id[0] = (char)dev; id[1] = (char)N;
-        memcpy(&id[2], key, 2 * NO);
-        return id;
+    KeyCurve c;
+    c.id_prefix = {(char)dev, (char)N};
+    c.key_len = 2 * NO; c.tab_bytes = TAB; c.aux_bytes = AUX; c.tab16_bytes = (size_t)N * 65536 * pt;
+    c.tab16_log2 = N == 8 ? 19 : 20;
+    c.on_curve_and_base = onekey_base<N>;
+    c.queue_build = [](hipStream_t st, const uint8_t *d_aux, uint8_t *d_tabs, size_t M) {
+        hipLaunchKernelGGL(bign_ktable_kernel<N>, dim3((unsigned)(((size_t)(2 * N + 1) * GT8_ENTRIES + 63) / 64), (unsigned)M), dim3(64), 0, st,
+                           reinterpret_cast<const uint4 *>(d_aux + 2 * NO), reinterpret_cast<uint4 *>(d_tabs), AUX / 16, TAB / 16);
     };
-    //  entries that leave the cache are parked here and released AFTER the lock is dropped (declared before the lock:
-    // destroyed after it): their destructors call hipFree, a device-wide wait, and every other key-table user would stall behind it
-    std::vector<std::shared_ptr<KeyTab>> dropped;
-    std::unique_lock<std::mutex> lk(g_keytab_mu);
-    std::vector<size_t> miss;                          // first occurrence of every key the cache does not hold
-    std::unordered_map<std::string, size_t> miss_at;   // id -> position in miss
-    std::vector<size_t> dup_of(nkeys, (size_t)-1);     // later occurrences of a missing key
-    for (size_t k = 0; k < nkeys; ++k) {
-        std::string id = id_of(keys + 2 * NO * k);
-        const auto it = g_keytabs.find(id);
-        if (it != g_keytabs.end()) {
-            KeyTab *t = it->second.get();
-            t->stamp = ++g_keytab_clock;
-            if (!capturing) t->used += n;
-            if (want16 && !t->tab16 && t->used >= after) { const err_t c = bign_key_table16_locked<N>(*t, st); if (c != ERR_OK) return c; }
-            out[k] = it->second;
-            continue;
-        }
-        const auto m = miss_at.find(id);
-        if (m != miss_at.end()) { dup_of[k] = miss[m->second]; continue; }
-        miss_at.emplace(std::move(id), miss.size());
-        miss.push_back(k);
-    }
-    if (!miss.empty()) {
-        {
-            // a key this process has not met needs an allocation, an upload and a synchronisation: none of that is legal on a stream
-            // that is being captured (and would kill the capture).  Say so instead: verify once under the key outside the capture.
-            if (capturing)
-                return hip_fail(hipErrorStreamCaptureUnsupported, "key-table miss under stream capture: verify once under each key before capturing");
-        }
-        // on the curve?  then the 2N + 1 starting points -- host threads when there are many keys
-        std::vector<std::vector<uint8_t>> base(miss.size());
-        std::vector<char> on_curve(miss.size(), 0);
-        std::atomic<int> threw{0};                     // (an exception must not leave a worker thread: bad_alloc in a resize)
-        const auto work = [&](size_t from, size_t to) {
-            try {
-                for (size_t i = from; i < to; ++i) on_curve[i] = onekey_base<N>(keys + 2 * NO * miss[i], base[i]) ? 1 : 0;
-            } catch (...) { threw.store(1); }
-        };
-        const size_t nthr = std::min<size_t>(16, miss.size() / 4);
-        if (nthr >= 2) {
-            std::vector<std::thread> th;
-            const size_t per = (miss.size() + nthr - 1) / nthr;
-            size_t started = 0;
-            try {
-                for (; started < nthr; ++started)
-                    th.emplace_back(work, std::min(miss.size(), started * per), std::min(miss.size(), (started + 1) * per));
-            } catch (...) {                            // no more threads to be had: the rest on this one
-                work(std::min(miss.size(), started * per), miss.size());
-            }
-            for (auto &t : th) t.join();
-        } else work(0, miss.size());
-        if (threw.load()) return ERR_OUTOFMEMORY;
-        std::vector<size_t> good;
-        for (size_t i = 0; i < miss.size(); ++i) if (on_curve[i]) good.push_back(i);
-        const auto evict_lru = [&]() -> bool {                  // the least recently used entry leaves the cache (freed when its last user lets go)
-            if (g_keytabs.empty()) return false;
-            auto old = g_keytabs.begin();
-            for (auto it = g_keytabs.begin(); it != g_keytabs.end(); ++it) if (it->second->stamp < old->second->stamp) old = it;
-            dropped.push_back(std::move(old->second));
-            g_keytabs.erase(old);
-            return true;
-        };
-        // The BYTE bound evicts by slab: a slab's memory returns only when ALL of its (<= 16) tables are gone and nobody
-        // holds one, so the unit that leaves is the idle slab whose most recent use is the oldest; when no idle slab is left the loop
-        // stops -- it never empties the cache without freeing a byte.  Returns the bytes that will be freed once `dropped` is released.
-        size_t pending_free = 0;
-        const auto evict_idle_slab = [&]() -> size_t {
-            struct Seen { uint64_t newest = 0; bool busy = false; };
-            std::unordered_map<const KeySlab *, Seen> slabs;
-            for (const auto &kv : g_keytabs) {
-                Seen &e = slabs[kv.second->slab.get()];
-                e.newest = std::max(e.newest, kv.second->stamp);
-                e.busy |= kv.second.use_count() != 1;       // a launcher (or a captured graph) holds this table
-            }
-            const KeySlab *victim = nullptr;
-            uint64_t oldest = ~(uint64_t)0;
-            for (const auto &kv : slabs) if (kv.first && !kv.second.busy && kv.second.newest < oldest) { oldest = kv.second.newest; victim = kv.first; }
-            if (!victim) return 0;
-            const size_t bytes = victim->bytes;
-            for (auto it = g_keytabs.begin(); it != g_keytabs.end();)
-                if (it->second->slab.get() == victim) { dropped.push_back(std::move(it->second)); it = g_keytabs.erase(it); } else ++it;
-            return bytes;
-        };
-        for (size_t g0 = 0; g0 < good.size(); g0 += KEYSLAB_KEYS) {
-            const size_t M = std::min(KEYSLAB_KEYS, good.size() - g0);
-            const size_t need = M * (TAB + AUX);
-            while (g_keyslab_bytes.load() - std::min(pending_free, g_keyslab_bytes.load()) + need > KEYTAB_BYTES_MAX) {
-                const size_t freed = evict_idle_slab();
-                if (!freed) break;
-                pending_free += freed;
-            }
-            auto slab = std::make_shared<KeySlab>();
-            if (hipMalloc(&slab->p, need) != hipSuccess) {
-                (void)hipGetLastError();
-                slab->p = nullptr;
-                // no room on the device: everything nobody is using right now goes -- released HERE, with the lock dropped, because the
-                // retry needs the memory back now -- then one more try.  (Another thread may cache one of this call's keys meanwhile:
-                // the assignment below then replaces its entry, which is harmless.)
-                for (auto it = g_keytabs.begin(); it != g_keytabs.end();)
-                    if (it->second.use_count() == 1) { dropped.push_back(std::move(it->second)); it = g_keytabs.erase(it); } else ++it;
-                lk.unlock();
-                dropped.clear();
-                pending_free = 0;
-                lk.lock();
-                if (hipMalloc(&slab->p, need) != hipSuccess) {
-                    (void)hipGetLastError();
-                    slab->p = nullptr;
-                    break;                                      // the remaining keys stay without a table: out[] = null, the callers' table-free paths
-                }
-            }
-            slab->bytes = need;
-            g_keyslab_bytes.fetch_add(need);
-            uint8_t *d_tabs = reinterpret_cast<uint8_t *>(slab->p), *d_aux = d_tabs + M * TAB;
-            std::vector<uint8_t> aux(M * AUX);
-            for (size_t j = 0; j < M; ++j) {
-                memcpy(aux.data() + j * AUX, keys + 2 * NO * miss[good[g0 + j]], 2 * NO);
-                memcpy(aux.data() + j * AUX + 2 * NO, base[good[g0 + j]].data(), AUX - 2 * NO);
-            }
-            B2H_TRY(hipMemcpyAsync(d_aux, aux.data(), aux.size(), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(bign_ktable_kernel<N>, dim3((unsigned)(((size_t)(2 * N + 1) * GT8_ENTRIES + 63) / 64), (unsigned)M), dim3(64), 0, st,
-                               reinterpret_cast<const uint4 *>(d_aux + 2 * NO), reinterpret_cast<uint4 *>(d_tabs), AUX / 16, TAB / 16);
-            B2H_TRY(hipGetLastError());
-            B2H_TRY(hipStreamSynchronize(st));          // (aux goes out of scope; other streams may use the tables next)
-            for (size_t j = 0; j < M; ++j) {
-                auto t = std::make_shared<KeyTab>();
-                t->slab = slab;
-                t->tab = reinterpret_cast<const uint4 *>(d_tabs + j * TAB);
-                t->d_key = d_aux + j * AUX;
-                t->stamp = ++g_keytab_clock;
-                t->used = n;
-                g_keytab_builds.fetch_add(1);
-                if (want16 && t->used >= after) { const err_t c = bign_key_table16_locked<N>(*t, st); if (c != ERR_OK) return c; }
-                if (g_keytabs.size() >= KEYTAB_SLOTS) evict_lru();
-                g_keytabs[id_of(keys + 2 * NO * miss[good[g0 + j]])] = t;
-                out[miss[good[g0 + j]]] = t;
-            }
-        }
-        for (size_t k = 0; k < nkeys; ++k) if (dup_of[k] != (size_t)-1) out[k] = out[dup_of[k]];
-    }
-    return ERR_OK;
+    c.queue_build16 = [](hipStream_t st, const void *tab, void *t16) {
+        hipLaunchKernelGGL(bign_gtable16_kernel<N>, dim3(N * 65536 / 256), dim3(256), 0, st, (const uint4 *)tab, (uint4 *)t16);
+    };
+    return g_keytab.tables(c, out, keys, nkeys, n, want16, st);
 }
 
 // keys: nkeys public keys on the host; d_key_index: null = ONE key (nkeys = 1), else n x uint32 on the device
@@ -2063,43 +1829,27 @@ static err_t launch_bign_verify_onekey_t(const uint8_t *oid_der, size_t oid_len,
         code = bign_table<N>(&gtab, st);
     }
     if (code != ERR_OK) return code;
-    std::vector<std::shared_ptr<KeyTab>> kts;
+    KeyTabCache::Tabs kts;
     // (keyed: every key is credited with its share of the batch -- the signers of a batch are taken to be about equally busy)
     code = bign_key_tables<N>(kts, keys, nkeys, keyed ? (n + nkeys - 1) / nkeys : n, true, st);
     if (code != ERR_OK) return code;
-    {
-        // A stream CAPTURE bakes the tables' addresses into the graph, and nothing tells the library when that graph dies: the tables
-        // a capture refers to are pinned for the life of the process (a reference that is never dropped), so neither the LRU nor a
-        // later call's eviction can free memory a replay will read.  Bounded by the distinct keys ever captured.
-        if (capturing) {
-            std::lock_guard<std::mutex> lk(g_keytab_mu);
-            static std::vector<std::shared_ptr<KeyTab>> &pinned = *new std::vector<std::shared_ptr<KeyTab>>;
-            for (const auto &t : kts)
-                if (t && std::find(pinned.begin(), pinned.end(), t) == pinned.end()) pinned.push_back(t);
-        }
-    }
-    const uint4 *tab16 = nullptr;
+    if (capturing) g_keytab.pin(kts);                              // (the graph keeps the tables' addresses)
+    const uint4 *tab = nullptr, *tab16 = nullptr;
     const uint8_t *d_keys = nullptr;
     const uint4 *const *d_tabs = nullptr;
     if (!keyed) {
         if (!kts[0]) return ERR_KEY_NOT_ON_CURVE;                  // (the caller's general path)
-        {
-            std::lock_guard<std::mutex> lk(g_keytab_mu);             // another thread may be giving the key its 16-bit table
-            tab16 = kts[0]->tab16;
-        }
+        const void *now[2];
+        g_keytab.view(kts, now, now + 1);
+        tab = static_cast<const uint4 *>(now[0]);
+        tab16 = static_cast<const uint4 *>(now[1]);
         d_keys = kts[0]->d_key;
     } else {
         // the tables' addresses (a key off the curve has none: null) and the keys go up in one block
         const size_t koff = (16 * nkeys + 15) & ~(size_t)15;       // (the kernels read keys with 16-octet loads)
         std::vector<uint8_t> blk(koff + 2 * NO * nkeys);
-        uint64_t *ptrs = reinterpret_cast<uint64_t *>(blk.data());
-        {
-            std::lock_guard<std::mutex> lk(g_keytab_mu);             // (another thread may be giving a key its 16-bit table)
-            for (size_t k = 0; k < nkeys; ++k) {
-                ptrs[k] = kts[k] ? (uint64_t)(uintptr_t)kts[k]->tab : 0;
-                ptrs[nkeys + k] = kts[k] ? (uint64_t)(uintptr_t)kts[k]->tab16 : 0;
-            }
-        }
+        const void **ptrs = reinterpret_cast<const void **>(blk.data());
+        g_keytab.view(kts, ptrs, ptrs + nkeys);
         memcpy(blk.data() + koff, keys, 2 * NO * nkeys);
         void *d_blk = nullptr;
         code = scratch_for_stream(st, 13, blk.size(), &d_blk);
@@ -2125,19 +1875,19 @@ static err_t launch_bign_verify_onekey_t(const uint8_t *oid_der, size_t oid_len,
                            (const uint4 *)nullptr, (const uint4 *)nullptr, (const uint32_t *)d_key_index, d_tabs, (uint32_t)nkeys);
     else if (quad && tab16)
         hipLaunchKernelGGL((bign_onekey4_kernel<N, VtOps, true, false>), dim3(g4), dim3(256), 0, st, dh, dsg, d_keys, n, S, (const uint4 *)gtab,
-                           kts[0]->tab, tab16, (const uint32_t *)nullptr, (const uint4 *const *)nullptr, 1u);
+                           tab, tab16, (const uint32_t *)nullptr, (const uint4 *const *)nullptr, 1u);
     else if (quad)
         hipLaunchKernelGGL((bign_onekey4_kernel<N, VtOps, false, false>), dim3(g4), dim3(256), 0, st, dh, dsg, d_keys, n, S, (const uint4 *)gtab,
-                           kts[0]->tab, (const uint4 *)nullptr, (const uint32_t *)nullptr, (const uint4 *const *)nullptr, 1u);
+                           tab, (const uint4 *)nullptr, (const uint32_t *)nullptr, (const uint4 *const *)nullptr, 1u);
     else if (keyed)
         hipLaunchKernelGGL((bign_onekey_kernel<N, VtOps, false, true>), dim3(g256), dim3(256), 0, st, dh, dsg, d_keys, n, S, (const uint4 *)gtab,
                            (const uint4 *)nullptr, (const uint4 *)nullptr, (const uint32_t *)d_key_index, d_tabs, (uint32_t)nkeys);
     else if (tab16)
         hipLaunchKernelGGL((bign_onekey_kernel<N, VtOps, true, false>), dim3(g256), dim3(256), 0, st, dh, dsg, d_keys, n, S, (const uint4 *)gtab,
-                           kts[0]->tab, tab16, (const uint32_t *)nullptr, (const uint4 *const *)nullptr, 1u);
+                           tab, tab16, (const uint32_t *)nullptr, (const uint4 *const *)nullptr, 1u);
     else
         hipLaunchKernelGGL((bign_onekey_kernel<N, VtOps, false, false>), dim3(g256), dim3(256), 0, st, dh, dsg, d_keys, n, S, (const uint4 *)gtab,
-                           kts[0]->tab, (const uint4 *)nullptr, (const uint32_t *)nullptr, (const uint4 *const *)nullptr, 1u);
+                           tab, (const uint4 *)nullptr, (const uint32_t *)nullptr, (const uint4 *const *)nullptr, 1u);
     hipLaunchKernelGGL(bign_slow_kernel<N>, dim3(g64), dim3(64), 0, st, dsg, d_keys, n, S, keyed ? ~(size_t)0 : (size_t)0);
     // shared inversions and the hash tail: as launch_bign_verify_t
     // (round 4: with the division-step inversion the optimum is flat; up to 2^17 signatures on the 256-bit curve 2^16

@@ -76,7 +76,10 @@ struct Global {
     std::mutex mu;
     std::vector<Stream *> streams;
     std::atomic<long> malloc_fail_in{0};       // the n-th device allocation from now fails (0 = off): tests of the out-of-memory paths
+    std::atomic<long> malloc_fail_len{1};      // ... and with it malloc_fail_len allocations in a row (a retry that is refused as well)
+    std::atomic<long> malloc_fail_more{0};
     std::atomic<long> live_device_blocks{0};
+    std::atomic<long> frees_started{0}, async_copies{0}, stream_syncs{0};      // calls so far: what a test may count
     int ndev = 2;
     Global() { if (const char *e = getenv("MOCKHIP_DEVICES")) ndev = atoi(e); }
 };
@@ -95,6 +98,17 @@ typedef mockhip::Event *hipEvent_t;
 static inline mockhip::Stream *mock_q(hipStream_t s) { return s ? s : mockhip::null_stream(); }
 // what a kernel launch is here: work queued on the stream, run later by the stream's thread
 static inline void mockhipLaunch(hipStream_t s, std::function<void()> f) { mock_q(s)->push(std::move(f)); }
+// a busy device on demand: a task that holds its stream -- and with it hipDeviceSynchronize and every hipFree -- until the latch opens
+namespace mockhip {
+struct Latch {
+    std::mutex mu;
+    std::condition_variable cv;
+    bool is_open = false;
+    void open() { std::lock_guard<std::mutex> lk(mu); is_open = true; cv.notify_all(); }
+    void wait() { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [this] { return is_open; }); }
+};
+}  // namespace mockhip
+static inline void mockhipBlock(hipStream_t s, mockhip::Latch *l) { mock_q(s)->push([l] { l->wait(); }); }
 
 static inline const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : e == hipErrorOutOfMemory ? "out of memory" : "mock hip error"; }
 static inline hipError_t hipGetLastError() { return hipSuccess; }
@@ -103,7 +117,11 @@ static inline hipError_t hipGetDeviceCount(int *n) { *n = mockhip::g().ndev; ret
 static inline hipError_t hipSetDevice(int d) { if (d < 0 || d >= mockhip::g().ndev) return hipErrorUnknown; mockhip::t_dev = d; return hipSuccess; }
 static inline hipError_t hipMalloc(void **p, size_t n)
 {
-    if (mockhip::g().malloc_fail_in.load() > 0 && mockhip::g().malloc_fail_in.fetch_sub(1) == 1) { *p = nullptr; return hipErrorOutOfMemory; }
+    mockhip::Global &G = mockhip::g();
+    if (G.malloc_fail_in.load() > 0 && G.malloc_fail_in.fetch_sub(1) == 1) { G.malloc_fail_more.store(G.malloc_fail_len.load() - 1); *p = nullptr; return hipErrorOutOfMemory; }
+    long more = G.malloc_fail_more.load();
+    while (more > 0 && !G.malloc_fail_more.compare_exchange_weak(more, more - 1)) {}
+    if (more > 0) { *p = nullptr; return hipErrorOutOfMemory; }
     *p = malloc(n ? n : 1);
     if (!*p) return hipErrorOutOfMemory;
     mockhip::g().live_device_blocks.fetch_add(1);
@@ -118,7 +136,11 @@ static inline hipError_t hipDeviceSynchronize()
     for (mockhip::Stream *s : mockhip::g().streams) s->drain();
     return hipSuccess;
 }
-static inline hipError_t hipFree(void *p) { if (p) { hipDeviceSynchronize(); free(p); mockhip::g().live_device_blocks.fetch_sub(1); } return hipSuccess; }
+static inline hipError_t hipFree(void *p)
+{
+    if (p) { mockhip::g().frees_started.fetch_add(1); hipDeviceSynchronize(); free(p); mockhip::g().live_device_blocks.fetch_sub(1); }
+    return hipSuccess;
+}
 static inline hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 static inline hipError_t hipHostFree(void *p) { free(p); return hipSuccess; }
 static inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned)
@@ -128,7 +150,7 @@ static inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned)
     mockhip::g().streams.push_back(*s);
     return hipSuccess;
 }
-static inline hipError_t hipStreamSynchronize(hipStream_t s) { mock_q(s)->drain(); return hipSuccess; }
+static inline hipError_t hipStreamSynchronize(hipStream_t s) { mockhip::g().stream_syncs.fetch_add(1); mock_q(s)->drain(); return hipSuccess; }
 static inline hipError_t hipStreamDestroy(hipStream_t s)
 {
     if (!s) return hipErrorUnknown;
@@ -143,6 +165,7 @@ static inline hipError_t hipStreamDestroy(hipStream_t s)
 }
 static inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t st)
 {
+    mockhip::g().async_copies.fetch_add(1);
     mock_q(st)->push([d, s, n] { memcpy(d, s, n); });
     return hipSuccess;
 }
