@@ -1782,6 +1782,7 @@ unsigned long long bign_onekey_tab16_live() { return (unsigned long long)g_keyta
 unsigned long long bign_onekey_table_builds() { return g_keytab.n.builds.load(); }
 void set_onekey_slots(int v) { g_keytab.slots = v < 1 ? 1 : (size_t)v; }
 void set_onekey_tab16(int v) { g_keytab.tab16_log2 = v; }
+void drop_onekey_tables() { g_keytab.drop_all(); }
 static int g_onekey_quads = -1;                      // four lanes per signature: -1 by batch size (<= 2^16), 0 never, 1 always (tests / A/B: tune 22)
 void set_onekey_quads(int v) { g_onekey_quads = v; }
 

@@ -149,6 +149,17 @@ public:
         }
     }
 
+    // Every entry leaves the cache (tests: a known starting state, room among the tab16_max).  As with an eviction, a table somebody
+    // still holds -- a launcher, a captured graph -- lives on until they let go; hipFree runs after the lock.
+    void drop_all()
+    {
+        Tabs gone;
+        std::lock_guard<std::mutex> lk(mu_);               // (gone is older than lk)
+        gone.reserve(map_.size());
+        for (auto &e : map_) gone.push_back(std::move(e.second));
+        map_.clear();
+    }
+
 private:
     struct Call {                                          // one call of tables()
         const KeyCurve &c;

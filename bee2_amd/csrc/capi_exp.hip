@@ -2,7 +2,7 @@
 #ifdef BEE2HIP_EXPERIMENTS      // everything from here to the end of the kernel-timing hook: libbee2hip_exp.so only
 // ============================================================ internal tuning hook ===
 // Tests force product paths and inject faults through it; not part of the product ABI (BEE2HIP_INTERNAL).
-namespace bee2hip { void set_verify_path(int v); void set_sign_coop(int v); void set_onekey_tab16(int v); void set_onekey_slots(int v); void set_onekey_quads(int v); }
+namespace bee2hip { void set_verify_path(int v); void set_sign_coop(int v); void set_onekey_tab16(int v); void set_onekey_slots(int v); void set_onekey_quads(int v); void drop_onekey_tables(); }
 extern "C" err_t bee2hip_internal_tune(int key, int value)
 try {
     switch (key) {
@@ -16,7 +16,8 @@ try {
     case 11: bee2hip::g_verify_pipe = value; return ERR_OK;           // chunked upload of big host-pointer verification batches
     case 22: bee2hip::set_onekey_quads(value); return ERR_OK;          // one-signer verification: four lanes per signature (-1 by size, 0 never, 1 always)
     case 21: bee2hip::set_onekey_slots(value); return ERR_OK;          // one-signer verification: keys the table cache keeps (tests: evictions under load)
-    case 20: bee2hip::set_onekey_tab16(value); return ERR_OK;          // one-signer verification: log2 of the signatures after which a key gets its 16-bit table (-1 by curve, 63 never)
+    case 23: bee2hip::drop_onekey_tables(); return ERR_OK;             // one-signer verification: every cached key table goes (tests: a known starting state; at most 96 keys hold a 16-bit table at a time)
+    case 20: bee2hip::set_onekey_tab16(value); return ERR_OK;         // one-signer verification: log2 of the signatures after which a key gets its 16-bit table (-1 by curve, 63 never)
     case 14: bee2hip::g_duplex_fail_chunk.store(value); return ERR_OK;   // tests: the duplex host pipeline fails at this chunk (1-based) ...
     case 15: bee2hip::g_duplex_fail_times.store(value); return ERR_OK;   // ... in the next `value` pipelines
     case 24: bee2hip::g_new_fail_in.store(value); return ERR_OK;       // tests: the value-th operator new of the library from now on throws std::bad_alloc (0 = off)

@@ -53,7 +53,7 @@ err_t bee2hip_internal_tune(int key, int value);
    signed 8-bit windows looked up in LDS, 256-bit curve only, elsewhere by size); key 11 = chunked upload of host-pointer
    verification batches of 2^19 signatures and more (1 = product); keys 14 / 15 = fault injection into the duplex host
    pipeline: the next `15` pipelines fail when they reach chunk `14`; keys 20 / 21 / 22 = one-signer verification: log2 of
-   the signatures after which a key gets its 16-bit table, keys the table cache keeps, four lanes per signature; key 24 =
+   the signatures after which a key gets its 16-bit table, keys the table cache keeps, four lanes per signature; key 23 = every cached key table is dropped; key 24 =
    the value-th operator new of the library from now on throws std::bad_alloc) */
 /* drop-in helper calls so far: which = 0 taken on the host path, 1 on the GPU, 2 finished on the host after the GPU path
    failed twice; 3 = key tables built so far and 5 = 16-bit key tables alive now (one-signer / few-signers verification);

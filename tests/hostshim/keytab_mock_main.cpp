@@ -254,6 +254,30 @@ static void slot_bound(hipStream_t st)
     CHECK(blocks() == base);
 }
 
+// ---- drop_all: every entry leaves, the 16-bit tables with them; a holder keeps a valid table; the keys are built again -------
+static void drop_all(hipStream_t st)
+{
+    const long base = blocks();
+    {
+        KeyTabCache cache;
+        small(cache);
+        cache.slots = 100;
+        Tabs held = get(cache, {K(1), K(2)}, 1024, true, st);          // busy on arrival: both have their 16-bit table
+        get(cache, {K(3), K(4), K(5)}, 1, true, st);
+        CHECK(cache.n.tab16_live.load() == 2);
+        held.resize(1);
+        cache.drop_all();
+        CHECK(cache.n.tab16_live.load() == 1 && intact(cache, held[0], K(1)) && has16(cache, held[0]));
+        held.clear();
+        CHECK(cache.n.tab16_live.load() == 0 && cache.n.slab_bytes.load() == 0 && blocks() == base);
+        const unsigned long long n0 = cache.n.builds.load();
+        CHECK(!cached(cache, K(1)) && !cached(cache, K(5)) && cache.n.builds.load() == n0 + 2);
+        cache.drop_all();
+        cache.drop_all();                                               // (empty: nothing to do)
+    }
+    CHECK(blocks() == base);
+}
+
 // ---- the byte bound: idle slabs leave, the one used longest ago first; nothing idle, nothing leaves -------------------------
 static void byte_bound(hipStream_t st)
 {
@@ -539,6 +563,7 @@ int main()
     miss_under_capture(st, cap);
     miss(st);
     slot_bound(st);
+    drop_all(st);
     byte_bound(st);
     slab_with_a_holder_outside(st);
     out_of_memory(st);
