@@ -482,17 +482,37 @@ void belt_che_kernel(const uint4 *__restrict__ src, uint4 *__restrict__ dst, uin
 // lanes take interleaved blocks (coalesced 1 KiB loads) and run Horner with the single fixed
 // multiplier R = r^64 (GfMulTab); at the end lane l scales by r^(63-l) and the wavefront XOR-reduces
 // to the chunk polynomial P_w = XOR_j X_j r^(end_w-1-j).  A chunk that is not a multiple of 64 blocks
-// is treated as left-padded with zero blocks.  polyhash_finish_kernel then weights every P_w with
+// is treated as left-padded with zero blocks.  polyhash_powers_kernel then weights every P_w with
 // r^(n - end_w + 1) and XORs everything, plus t * r^n, into the 16-byte result.
 //
-// consts[l] = r^(63-l) for l < 64, consts[64] = r^64.
+// polyhash_powers_kernel, one thread per power of r, runs before polyhash_kernel and after it -- one kernel, the step a launch
+// argument the whole grid agrees on and tests once, at its top:
+//   consts != null (before; one workgroup of 128): consts[l] = r^(63-l) for l < 64, consts[64] = r^64
+//   consts == null (after; workgroups of 64): out (zeroed before) ^= P_w * r^(n - end_w + 1) for every chunk, and ^= t * r^n
 __global__ __launch_bounds__(128)
-void polyhash_prep_kernel(BeltCtr r, uint4 *__restrict__ consts)
+void polyhash_powers_kernel(const uint4 *__restrict__ partial, unsigned nwaves, uint64_t chunk, uint64_t nblocks,
+                            BeltCtr r, BeltCtr t_in, uint32_t *__restrict__ out, uint4 *__restrict__ consts)
 {
-    const unsigned l = threadIdx.x;
-    if (l > 64) return;
     const Gf128 rr = gf_from(make_uint4(r.c[0], r.c[1], r.c[2], r.c[3]));
-    consts[l] = gf_to(gf_pow(rr, l < 64 ? 63 - l : 64));
+    if (consts) {
+        const unsigned l = threadIdx.x;
+        if (l > 64) return;
+        consts[l] = gf_to(gf_pow(rr, l < 64 ? 63 - l : 64));
+        return;
+    }
+    const unsigned w = blockIdx.x * 64 + threadIdx.x;
+    if (w > nwaves) return;
+    Gf128 v;
+    if (w < nwaves) {
+        const uint64_t c0 = (uint64_t)w * chunk;
+        if (c0 >= nblocks) return;
+        const uint64_t end = c0 + chunk <= nblocks ? c0 + chunk : nblocks;
+        v = gf_mul(gf_from(partial[w]), gf_pow(rr, nblocks - end + 1));
+    } else {
+        v = gf_mul(gf_from(make_uint4(t_in.c[0], t_in.c[1], t_in.c[2], t_in.c[3])), gf_pow(rr, nblocks));
+    }
+    atomicXor(out + 0, (uint32_t)v.lo); atomicXor(out + 1, (uint32_t)(v.lo >> 32));
+    atomicXor(out + 2, (uint32_t)v.hi); atomicXor(out + 3, (uint32_t)(v.hi >> 32));
 }
 
 constexpr int PH_WG = 256;
@@ -539,27 +559,6 @@ void polyhash_kernel(const uint8_t *__restrict__ data, uint64_t nbytes, uint64_t
         x2 ^= __shfl_xor(x2, m, 64); x3 ^= __shfl_xor(x3, m, 64);
     }
     if (lane == 0) partial[w] = make_uint4(x0, x1, x2, x3);
-}
-
-// out (zeroed before) ^= P_w * r^(n - end_w + 1) for every chunk, and ^= t * r^n
-__global__ __launch_bounds__(64)
-void polyhash_finish_kernel(const uint4 *__restrict__ partial, unsigned nwaves, uint64_t chunk, uint64_t nblocks,
-                            BeltCtr r, BeltCtr t_in, uint32_t *__restrict__ out)
-{
-    const unsigned w = blockIdx.x * 64 + threadIdx.x;
-    if (w > nwaves) return;
-    const Gf128 rr = gf_from(make_uint4(r.c[0], r.c[1], r.c[2], r.c[3]));
-    Gf128 v;
-    if (w < nwaves) {
-        const uint64_t c0 = (uint64_t)w * chunk;
-        if (c0 >= nblocks) return;
-        const uint64_t end = c0 + chunk <= nblocks ? c0 + chunk : nblocks;
-        v = gf_mul(gf_from(partial[w]), gf_pow(rr, nblocks - end + 1));
-    } else {
-        v = gf_mul(gf_from(make_uint4(t_in.c[0], t_in.c[1], t_in.c[2], t_in.c[3])), gf_pow(rr, nblocks));
-    }
-    atomicXor(out + 0, (uint32_t)v.lo); atomicXor(out + 1, (uint32_t)(v.lo >> 32));
-    atomicXor(out + 2, (uint32_t)v.hi); atomicXor(out + 3, (uint32_t)(v.hi >> 32));
 }
 
 // CBC encryption is a serial chain per message (belt_cbc.c:63-84): one lane per message,
@@ -859,13 +858,14 @@ err_t launch_belt_polyhash(const void *d_data, size_t nbytes, const uint32_t r[4
     uint4 *consts = (uint4 *)scr, *partial = consts + 65;
     B2H_TRY(hipMemsetAsync(d_t_out, 0, 16, st));
     if (nwaves) {
-        hipLaunchKernelGGL(polyhash_prep_kernel, dim3(1), dim3(128), 0, st, rr, consts);
+        hipLaunchKernelGGL(polyhash_powers_kernel, dim3(1), dim3(128), 0, st, (const uint4 *)nullptr, 0u, (uint64_t)0, (uint64_t)0,
+                           rr, tt, (uint32_t *)nullptr, consts);
         const size_t wg_waves = PH_WG / 64;
         hipLaunchKernelGGL(polyhash_kernel, dim3((unsigned)((nwaves + wg_waves - 1) / wg_waves)), dim3(PH_WG), 0, st,
                            (const uint8_t *)d_data, (uint64_t)nbytes, chunk, (const uint4 *)consts, partial);
     }
-    hipLaunchKernelGGL(polyhash_finish_kernel, dim3((unsigned)((nwaves + 1 + 63) / 64)), dim3(64), 0, st,
-                       (const uint4 *)partial, (unsigned)nwaves, chunk, nblocks, rr, tt, (uint32_t *)d_t_out);
+    hipLaunchKernelGGL(polyhash_powers_kernel, dim3((unsigned)((nwaves + 1 + 63) / 64)), dim3(64), 0, st,
+                       (const uint4 *)partial, (unsigned)nwaves, chunk, nblocks, rr, tt, (uint32_t *)d_t_out, (uint4 *)nullptr);
     B2H_TRY(hipGetLastError());
     return ERR_OK;
 }

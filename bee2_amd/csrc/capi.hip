@@ -15,6 +15,7 @@
 //   capi_prg.hip    bash-prg (prg-hash, prg-ae) over ragged batches
 //   capi_beltae.hip belt-dwp / belt-che over ragged batches of records
 //   capi_fmt.hip    belt-fmt over batches of records, beltFMTEncr / beltFMTDecr
+//   capi_kwp.hip    belt-kwp over batches of keys of one length
 //   capi_exp.hip    experiment hooks (libbee2hip_exp.so only)
 #include "staging.hpp"
 static const bool g_capture_query_set = (bee2hip::g_stream_capturing = bee2hip::stream_is_capturing, true);
@@ -26,4 +27,5 @@ static const bool g_capture_query_set = (bee2hip::g_stream_capturing = bee2hip::
 #include "capi_prg.hip"
 #include "capi_beltae.hip"
 #include "capi_fmt.hip"
+#include "capi_kwp.hip"
 #include "capi_exp.hip"

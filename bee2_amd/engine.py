@@ -22,6 +22,7 @@ ERR_BAD_PARAMS = 502
 ERR_BAD_PUBKEY = 505
 ERR_BAD_SIG = 510
 ERR_BAD_MAC = 511
+ERR_BAD_KEYTOKEN = 513
 ERR_BEE2HIP_DEVICE = 0x4850
 
 OID_BELT_HASH_DER = bytes.fromhex("06092A7000020022651F51")   # bign128.c:151-153
@@ -101,6 +102,7 @@ BATCH_SYMBOLS = [
     "bee2hip_bashPrgHash_ragged_stream", "bee2hip_bashPrgAE_ragged_stream",
     "bee2hip_beltAE_wrap_ragged", "bee2hip_beltAE_unwrap_ragged", "bee2hip_beltAE_ragged_stream",
     "bee2hip_beltFMT_batch", "bee2hip_beltFMT_batch_stream",
+    "bee2hip_beltKWP_wrap_batch", "bee2hip_beltKWP_unwrap_batch", "bee2hip_beltKWP_batch_stream",
     "bee2hip_set_device", "bee2hip_sync", "bee2hip_last_error", "bee2hip_version", "bee2hip_path_policy", "bee2hip_path_count",
 ]
 # include/bee2hip_internal.h: test / bench hooks, not product ABI
@@ -397,6 +399,14 @@ class Engine:
             ctypes.c_int(1 if decr else 0), _u32(mod), _sz(count), bytes(key), _sz(len(key)), self._optr(ivs), self._optr(src),
             _sz(n), self._optr(dst), self._stream()), "beltFMT_batch_stream")
 
+    def beltKWP_batch_stream(self, unwrap, key, hdrs, src, count, n, dst, codes=None):
+        """belt-kwp over n records of `count` octets (wrap: the keys, unwrap: the tokens): hdrs (u8, n*16, or None: all zero),
+        src, dst (n*(count+16) for wrap, n*(count-16) for unwrap) and codes (int32, n: unwrap only) are device tensors; key
+        (bytes) is shared by the batch"""
+        self._check(self.lib.bee2hip_beltKWP_batch_stream(
+            ctypes.c_int(unwrap), bytes(key), _sz(len(key)), self._optr(hdrs), self._optr(src), _sz(count), _sz(n),
+            self._optr(dst), self._optr(codes), self._stream()), "beltKWP_batch_stream")
+
     def time_kernel(self, which, reps, a=None, b=None, c=None, d=None, n=0, aux=0):
         ms = ctypes.c_float(0)
         p = [self._ptr(t) if t is not None else None for t in (a, b, c, d)]
@@ -546,6 +556,25 @@ class Engine:
         code = self.lib.bee2hip_beltFMT_batch(ctypes.c_int(decr), _u32(mod), _sz(count), bytes(key), _sz(len(key)),
                                               None if ivs is None else bytes(ivs), bytes(records), _sz(n), dst)
         return code, dst.raw[:len(records)]
+
+    def beltKWP_wrap_batch(self, key, hdrs, records, count):
+        """belt-kwp: records = n * count octets, hdrs = n * 16 octets or None -> (code, n * (count + 16) octets of tokens)"""
+        n = len(records) // count
+        assert len(records) == count * n and (hdrs is None or len(hdrs) == 16 * n)
+        dst = ctypes.create_string_buffer(max(1, n * (count + 16)))
+        code = self.lib.bee2hip_beltKWP_wrap_batch(bytes(key), _sz(len(key)), None if hdrs is None else bytes(hdrs), bytes(records),
+                                                   _sz(count), _sz(n), dst)
+        return code, dst.raw[:n * (count + 16)]
+
+    def beltKWP_unwrap_batch(self, key, hdrs, tokens, count):
+        """tokens = n * count octets -> (code, n * (count - 16) octets: the keys, zeros where refused,
+        [ERR_OK / ERR_BAD_KEYTOKEN per record])"""
+        n = len(tokens) // count
+        assert len(tokens) == count * n and (hdrs is None or len(hdrs) == 16 * n)
+        dst, codes = ctypes.create_string_buffer(max(1, n * (count - 16))), (_u32 * max(n, 1))()
+        code = self.lib.bee2hip_beltKWP_unwrap_batch(bytes(key), _sz(len(key)), None if hdrs is None else bytes(hdrs), bytes(tokens),
+                                                     _sz(count), _sz(n), dst, codes)
+        return code, dst.raw[:n * (count - 16)], list(codes)[:n]
 
     # ------------------------------------------------- bee2 drop-in interface
     def beltFMT(self, decr, mod, symbols, key, iv=None):

@@ -73,6 +73,7 @@ typedef uint32_t err_t;
 #define ERR_BAD_PUBKEY       ((err_t)505)   /* err.h:186 */
 #define ERR_BAD_SIG          ((err_t)510)   /* err.h:196 */
 #define ERR_BAD_MAC          ((err_t)511)   /* err.h:198 */
+#define ERR_BAD_KEYTOKEN     ((err_t)513)   /* err.h */
 /* engine-specific: a HIP runtime call failed (no bee2 equivalent; the reference
    has no device).  bee2hip_last_error() returns the HIP message. */
 #define ERR_BEE2HIP_DEVICE   ((err_t)0x4850)
@@ -428,6 +429,35 @@ err_t bee2hip_beltFMT_batch_stream(int decr, u32 mod, size_t count, const octet 
    DIFFERENCE FROM bee2: a mod outside 2 .. 65536 is ERR_BAD_INPUT here; bee2 only asserts it. */
 err_t beltFMTEncr(u16 dest[], u32 mod, const u16 src[], size_t count, const octet key[], size_t len, const octet iv[16]);
 err_t beltFMTDecr(u16 dest[], u32 mod, const u16 src[], size_t count, const octet key[], size_t len, const octet iv[16]);
+
+/* ---- belt-kwp: key wrap of n keys of one length (STB 34.101.31; belt.h, src/crypto/belt/belt_kwp.c) ------------------
+   Record by record these are bee2's one-shots
+       beltKWPWrap(dst_i, src_i, count, hdr_i, key, key_len)  and  beltKWPUnwrap(dst_i, src_i, count, hdr_i, key, key_len);
+   all n records have the same count and the same key-encryption key.  One lane of belt_kwp_batch_kernel per record.
+   wrap: record i is the `count` >= 16 octets src + i * count (any values), its header hdrs + 16 i (hdrs == NULL: every header is
+   16 zero octets, as bee2's header == 0), its token the count + 16 octets dst + i * (count + 16).
+   unwrap: record i is the token src + i * count, count >= 32; the result is the count - 16 octets dst + i * (count - 16) and
+   codes[i] is ERR_OK or ERR_BAD_KEYTOKEN.  The 16 octets of the recovered header are all compared with hdrs + 16 i (no early
+   exit); the result octets of a refused record are ZEROS, as belt_kwp.c:84, and its neighbours are untouched.
+   Tokens of up to 1024 octets: a wrap count above 1008 or an unwrap count above 1024 is ERR_NOT_IMPLEMENTED.  Before any
+   device work: ERR_BAD_INPUT for a count below the minimum, a key_len other than 16, 24 or 32, a NULL key, n >= 2^32, or
+   a NULL src, dst or (unwrap) codes with n > 0; n = 0 is ERR_OK without a device.  The two host forms stage both buffers, so
+   their dst may be src; the stream form below refuses any overlap.
+   The bee2 names themselves are not exported: a single token is one serial chain of E_K. */
+err_t bee2hip_beltKWP_wrap_batch(const octet key[], size_t key_len, const octet *hdrs, const octet *src, size_t count, size_t n,
+                                 octet *dst);
+err_t bee2hip_beltKWP_unwrap_batch(const octet key[], size_t key_len, const octet *hdrs, const octet *src, size_t count, size_t n,
+                                   octet *dst, err_t *codes);
+/* The same on device pointers, asynchronous on `stream` (one queue, no fork; may be captured into a graph); unwrap = 0 or 1,
+   anything else is ERR_BAD_INPUT.  The suffix is _stream for the reason given at bee2hip_beltAE_ragged_stream;
+   tests/test_gpu_beltkwp.py holds the entry to the device-pointer contract.  key is a HOST pointer: it is expanded on the host
+   and travels in the launch arguments.  d_src, d_dst and d_hdrs need no alignment; d_codes (n x err_t, unwrap only; may be
+   NULL for wrap) is 4-aligned.  The fast path is count % 4 == 0 with a 4-aligned base: d_src and d_dst, each on its own, then move as
+   dwords, otherwise octet by octet (about 4 % of the rate at count 19 against 24); headers are always read octet by octet.
+   Source and result differ in size, so nothing is in place: ANY overlap of the src and dst
+   ranges is ERR_BAD_INPUT with nothing written; d_hdrs and d_codes must not meet d_dst either (not checked). */
+err_t bee2hip_beltKWP_batch_stream(int unwrap, const octet key[], size_t key_len, const void *d_hdrs, const void *d_src,
+                                   size_t count, size_t n, void *d_dst, void *d_codes, void *stream);
 
 /* ---- one host batch over several GPUs from one process --------------------------------
    The batch is cut into contiguous index ranges (bee2hip_multi_plan), one worker thread per device runs the
