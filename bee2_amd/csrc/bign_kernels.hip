@@ -54,6 +54,7 @@
 #include "bign_quad29.hpp"
 #include "common.hpp"
 #include "bign_keytab.hpp"         // the one-signer table cache; device_table_once
+#include "bign_plan.hpp"           // which kernels a batch runs: the thresholds and the tests' overrides
 #include "host_bign.hpp"          // host arithmetic of the one-signer path: the points 2^(8 w) Q (verification: no secrets)
 #include "bign_curves.inc"
 
@@ -1311,6 +1312,7 @@ void bign_onekey4_kernel(const uint8_t *__restrict__ hashes, const uint8_t *__re
 // windows pay.
 template <int N> struct Win6 { static constexpr int W = (32 * N + 1 + 5) / 6; };
 template <int N, int WB> struct WinW { static constexpr int W = (32 * N + 1 + WB - 1) / WB, ENT = 1 << (WB - 1); };
+template <int N> constexpr size_t MULBASE_LDS_BYTES = (size_t)WinW<N, 8>::ENT * N * 8 * 16;   // dynamic LDS of bign_mulbase_lds_kernel: 128 entries x 64 octets x 16 copies (N = 8)
 template <int N, int WB = 6>
 __global__ __launch_bounds__(64)
 void bign_gtable6_kernel(const uint4 *__restrict__ gtab8, uint4 *__restrict__ gtab6)
@@ -1595,8 +1597,32 @@ static err_t bign_scratch(hipStream_t st, size_t n, VerifyScratch &S)
     return ERR_OK;
 }
 
-static int g_verify_path = 0, g_verify_lanes = 0;
-void set_verify_path(int v) { g_verify_path = v & 15; g_verify_lanes = v >> 4; }   // 0x43: quads at every size
+// ---- which kernels run is bign_plan.hpp's business; the launchers below ask it once and launch what it says ------------------------
+static BignForce g_force;                            // what the tests force (tune 2, 22, 10; bign_sign_kernels.hip reads sign_lanes)
+void set_verify_path(int v) { g_force.set_verify(v); }
+
+// what every verification ends with: flagged lanes by the complete formulas, x_R = X / Z^2 with shared inversions, the hash tail.
+// keys / key_bytes: the slow kernel's keys and their stride (2 NO; one signer 0; keyed ~0: through the key index)
+template <int N>
+static err_t verify_finish(const FinishPlan &F, const uint8_t *dh, const uint8_t *dsg, const uint8_t *keys, size_t key_bytes, size_t n,
+                           const VerifyScratch &S, const OidArg &oid, void *d_codes, hipStream_t st)
+{
+    const unsigned g64 = (unsigned)((n + 63) / 64);
+    hipLaunchKernelGGL(bign_slow_kernel<N>, dim3(g64), dim3(64), 0, st, dsg, keys, n, S, key_bytes);
+    hipLaunchKernelGGL(bign_inv_kernel<N>, dim3((unsigned)((F.inv_lanes + 63) / 64)), dim3(64), 0, st, n, F.inv_lanes, (int)F.k_inv, S);
+    constexpr size_t row_bytes = (2 * N + 1) * 4;
+    if (F.tail_wide) {
+        auto kern = bign_tail_kernel<N, BeltTabTwoP, 1024>;
+        const size_t lds = BeltTabTwo::kBytes + 1024 * row_bytes;
+        B2H_TRY(dyn_lds_once(reinterpret_cast<const void *>(kern), lds));
+        hipLaunchKernelGGL(kern, dim3((unsigned)((n + 1023) / 1024)), dim3(1024), lds, st, dh, dsg, n, S, oid, (uint32_t *)d_codes);
+    } else {
+        hipLaunchKernelGGL((bign_tail_kernel<N, BeltTabSmall, 64>), dim3(g64), dim3(64), BeltTabSmall::kBytes + 64 * row_bytes, st,
+                           dh, dsg, n, S, oid, (uint32_t *)d_codes);
+    }
+    B2H_TRY(hipGetLastError());
+    return ERR_OK;
+}
 
 template <int N>
 static err_t launch_bign_verify_t(const uint8_t *oid_der, size_t oid_len, const void *d_hashes, const void *d_sigs,
@@ -1615,105 +1641,44 @@ static err_t launch_bign_verify_t(const uint8_t *oid_der, size_t oid_len, const 
     OidArg oid;
     code = make_oid_arg(oid, oid_der, oid_len, st);
     if (code != ERR_OK) return code;
-    constexpr size_t NO_ = 4 * N;
-    const unsigned g256 = (unsigned)((n + 255) / 256), g64 = (unsigned)((n + 63) / 64);
-    const size_t sp = n >= ((size_t)1 << 18) ? 2 : 1;           // signatures per lane in prep (shared inversion)
-    const size_t plan = (n + sp - 1) / sp;
-    // Which kernels walk the scalar multiplication (g_verify_path: 0 by size, 1 always the 32-bit
-    // kernels, 2 the 29-bit main kernel, 3 the quad / pair kernel, + 16 x lanes to force quads (0x43), pairs (0x23) or quads with a helper quad (0x83; 0x93 / 0xA3 with 64 / 256 lanes per block)
-    // -- tests and A/B):
-    //   <= 2^14 signatures: one signature per quad, 29-bit limbs (prep + main in one kernel, no table inversion)
-    //   <= 2^15           : one signature per pair of lanes, same kernel (256-bit curve; the wider ones use quads up
-    //                       to 2^14 and the 32-bit kernels above: 28- / 27-bit limbs, LZ<N>)
-    //   <= 2^18           : one lane per signature, 29-bit limbs, the multiplication one asm block (bign_fe29_asm.inc; round 6: it
-    //                       beats the 32-bit kernels at four wavefronts per SIMD too: 1 662 against 1 768 us at 2^18)
-    //   above             : one lane per signature, 32-bit limbs (the throughput form)
-    int path = 1;
-    if constexpr (N == 8) path = g_verify_path ? g_verify_path : n <= ((size_t)1 << 15) ? 3 : n <= ((size_t)1 << 18) ? 2 : 1;   // (round 6: the 29-bit kernel's multiplication is one asm block now -- it beats the 32-bit kernels up to 2^18: profiles/r06_f29_asm_ab.txt)
-    // wider curves, quads only: up to 2^14 signatures they leave one wavefront per SIMD; up to 2^15 two, which costs twice
-    // the time (2.4 / 4.7 ms) and still beats the one-lane kernels' latency floor (3.4 / 6.7 ms, profiles/r03_verify_wide.txt)
-    else path = g_verify_path == 1 || g_verify_path == 3 ? g_verify_path : n <= ((size_t)1 << 15) ? 3 : 1;
-    if (path == 3) {
-        const auto launch = [&](auto kern, unsigned wg, unsigned lanes) -> err_t {
-            const unsigned ns = wg / lanes;
-            const size_t lds = (size_t)8 * 4 * LZ<N>::L * ns * 4;
-            if (lds > 48 * 1024) B2H_TRY(dyn_lds_once(reinterpret_cast<const void *>(kern), lds));   // once per (device, kernel)
-            hipLaunchKernelGGL(kern, dim3((unsigned)((n + ns - 1) / ns)), dim3(wg), lds, st, (const uint8_t *)d_hashes,
-                               (const uint8_t *)d_sigs, (const uint8_t *)d_pubkeys, n, S, (const uint4 *)gtab);
-            return ERR_OK;
-        };
-        int lanes = 4;
-        if constexpr (N == 8) lanes = g_verify_lanes == 2 ? 2 : g_verify_lanes ? 4 : n <= ((size_t)1 << 14) ? 4 : 2;
-        if constexpr (N == 8) {
-            if (lanes == 2) code = launch(bign_quad29_kernel<8, 256, 2>, 256, 2);
+    const uint8_t *dh = (const uint8_t *)d_hashes, *dsg = (const uint8_t *)d_sigs, *dpk = (const uint8_t *)d_pubkeys;
+    const unsigned g256 = (unsigned)((n + 255) / 256);
+    const VerifyPlan P = verify_plan(N, n, g_force);
+    const auto quads = [&](auto kern) -> err_t {
+        const unsigned ns = (unsigned)(P.wg / P.lanes);
+        const size_t lds = (size_t)8 * 4 * LZ<N>::L * ns * 4;
+        if (lds > 48 * 1024) B2H_TRY(dyn_lds_once(reinterpret_cast<const void *>(kern), lds));   // once per (device, kernel)
+        hipLaunchKernelGGL(kern, dim3((unsigned)((n + ns - 1) / ns)), dim3((unsigned)P.wg), lds, st, dh, dsg, dpk, n, S, (const uint4 *)gtab);
+        return ERR_OK;
+    };
+    // (the kernels are named in the order the code object lays them out: moving a name moves every kernel behind it)
+    switch (P.walk) {
+    case Walk::QUAD:
+        if (P.lanes == 2) {
+            if constexpr (N == 8) code = quads(bign_quad29_kernel<8, 256, 2>);      // (pairs: the 256-bit curve only)
         }
-        if (lanes != 2) {
-            // up to 2^13 signatures a helper quad per signature takes the comb of u off the main quad's chain (x1.05, x1.10
-            // at 2^13).  Four-wave blocks, because wavefronts of a block share a CU's instruction fetches and this
-            // kernel is long; around 2^12 one-wave blocks spread over all CUs win (tools/ab/verify_helper_ab.py).
-            const bool helper = g_verify_lanes >= 8 || (g_verify_lanes == 0 && n <= ((size_t)1 << 13));
-            const bool one_wave = g_verify_lanes == 9 || (g_verify_lanes != 10 && n > ((size_t)3 << 10) && n <= ((size_t)1 << 12));
-            if (helper && one_wave) code = launch(bign_quad29_kernel<N, 64, 8>, 64, 8);
-            else if (helper) code = launch(bign_quad29_kernel<N, 256, 8>, 256, 8);
-            else code = launch(bign_quad29_kernel<N, 256, 4>, 256, 4);      // (also what 0x43 forces at every size)
-        }
+        else if (P.lanes == 8 && P.wg == 64) code = quads(bign_quad29_kernel<N, 64, 8>);
+        else if (P.lanes == 8) code = quads(bign_quad29_kernel<N, 256, 8>);
+        else code = quads(bign_quad29_kernel<N, 256, 4>);
         if (code != ERR_OK) return code;
-    }
-    if (path != 3) {
-        // The MAIN kernel takes its multiply-adds in pairs (VtOpsP, bign_dev.hpp mac2) where that pays -- measured,
-        // profiles/r04_mad_pairs_vt.txt: the 384- / 512-bit curves up to 2^16 signatures (ONE wavefront per SIMD: 2.85 -> 2.14 ms and
-        // 6.26 -> 4.82 ms at 2^16), the 256-bit curve from 2^18 on (four wavefronts: +0.8 % at 2^18, +1.7 % at 2^19); at two wavefronts
-        // per SIMD the paired form loses 2-5 % on every curve, and points / prep do not care.
-        const bool pair_main = N == 8 ? n >= ((size_t)1 << 18) : n <= ((size_t)1 << 16);
-        if constexpr (N != 8)
-            hipLaunchKernelGGL((bign_points_kernel<N>), dim3(g256), dim3(256), 0, st, (const uint8_t *)d_hashes,
-                               (const uint8_t *)d_sigs, (const uint8_t *)d_pubkeys, n, S);
-        hipLaunchKernelGGL((bign_prep_kernel<N>), dim3((unsigned)((plan + 255) / 256)), dim3(256), 0, st,
-                           (const uint8_t *)d_hashes, (const uint8_t *)d_sigs, (const uint8_t *)d_pubkeys, n, plan,
-                           (int)sp, S);
-        if constexpr (N == 8) {
-            if (path == 2) {
-                const unsigned wg = n <= ((size_t)1 << 14) ? 64u : 256u;
-                hipLaunchKernelGGL(bign_main29_kernel, dim3((unsigned)((n + wg - 1) / wg)), dim3(wg), 0, st, n, S,
-                                   (const uint4 *)gtab);
+        break;
+    case Walk::LANE29:
+    case Walk::LANE32: {
+        const size_t lanes = (n + P.sp - 1) / P.sp;
+        if constexpr (N != 8) hipLaunchKernelGGL((bign_points_kernel<N>), dim3(g256), dim3(256), 0, st, dh, dsg, dpk, n, S);
+        hipLaunchKernelGGL((bign_prep_kernel<N>), dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, dh, dsg, dpk, n, lanes, P.sp, S);
+        if (P.walk == Walk::LANE29) {
+            if constexpr (N == 8) {
+                const unsigned wg = (unsigned)P.main29_wg;
+                hipLaunchKernelGGL(bign_main29_kernel, dim3((unsigned)((n + wg - 1) / wg)), dim3(wg), 0, st, n, S, (const uint4 *)gtab);
             }
         }
-        if (path != 2) {
-            bool main_done = false;
-            if (pair_main) {
-                hipLaunchKernelGGL((bign_main_kernel<N, VtOpsP>), dim3(g256), dim3(256), 0, st, n, S, (const uint4 *)gtab);
-                main_done = true;
-            }
-            if (!main_done) hipLaunchKernelGGL((bign_main_kernel<N, VtOps>), dim3(g256), dim3(256), 0, st, n, S, (const uint4 *)gtab);
-        }
+        else if (P.pair_main) hipLaunchKernelGGL((bign_main_kernel<N, VtOpsP>), dim3(g256), dim3(256), 0, st, n, S, (const uint4 *)gtab);
+        else hipLaunchKernelGGL((bign_main_kernel<N, VtOps>), dim3(g256), dim3(256), 0, st, n, S, (const uint4 *)gtab);
+        break;
     }
-    hipLaunchKernelGGL(bign_slow_kernel<N>, dim3(g64), dim3(64), 0, st, (const uint8_t *)d_sigs,
-                       (const uint8_t *)d_pubkeys, n, S, (size_t)(2 * NO_));
-    // signatures per inversion.  Each lane runs one chain (division steps, then 5 multiplications per
-    // signature) and a lone wavefront issues at about a third of a SIMD's rate, so fewer, longer lanes cost
-    // little until the lanes no longer cover the SIMDs: measured best at 2^18 signatures K = 8 on the 256-bit
-    // curve (72 us; K = 2: 105 us) and K = 4 on the wider ones (profiles/r01_bign_ab_inv.txt)
-    // (round 4: with the division-step inversion the optimum is flat; up to 2^17 signatures on the 256-bit curve 2^16
-    //  lanes -- one wavefront per SIMD, two signatures each -- are 4-7 % ahead of 2^15; profiles/r04_inv_lanes_ab.txt)
-    const size_t inv_lanes = N == 8 && n > ((size_t)1 << 17) ? 32768 : 65536;
-    const size_t k_inv = std::min<size_t>(16, std::max<size_t>(1, n / inv_lanes));
-    const size_t lanes = (n + k_inv - 1) / k_inv;
-    hipLaunchKernelGGL(bign_inv_kernel<N>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, n, lanes,
-                       (int)k_inv, S);
-    constexpr size_t row_bytes = (2 * N + 1) * 4;
-    if (N == 8 && n >= 65536) {
-        auto kern = bign_tail_kernel<N, BeltTabTwoP, 1024>;
-        const size_t lds = BeltTabTwo::kBytes + 1024 * row_bytes;
-        B2H_TRY(dyn_lds_once(reinterpret_cast<const void *>(kern), lds));
-        hipLaunchKernelGGL(kern, dim3((unsigned)((n + 1023) / 1024)), dim3(1024), lds, st, (const uint8_t *)d_hashes,
-                           (const uint8_t *)d_sigs, n, S, oid, (uint32_t *)d_codes);
-    } else {
-        hipLaunchKernelGGL((bign_tail_kernel<N, BeltTabSmall, 64>), dim3(g64), dim3(64),
-                           BeltTabSmall::kBytes + 64 * row_bytes, st, (const uint8_t *)d_hashes,
-                           (const uint8_t *)d_sigs, n, S, oid, (uint32_t *)d_codes);
     }
-    B2H_TRY(hipGetLastError());
-    return ERR_OK;
+    return verify_finish<N>(P.fin, dh, dsg, dpk, 2 * 4 * N, n, S, oid, d_codes, st);
 }
 
 // l = security level (128, 192, 256): hashes n*(l/4), sigs n*(3l/8), pubkeys n*(l/2) octets
@@ -1722,10 +1687,7 @@ err_t launch_bign_verify(size_t l, const uint8_t *oid_der, size_t oid_len, const
                          hipStream_t st)
 {
     if (n == 0) return ERR_OK;
-    if (l == 128) return launch_bign_verify_t<8>(oid_der, oid_len, d_hashes, d_sigs, d_pubkeys, n, d_codes, st);
-    if (l == 192) return launch_bign_verify_t<12>(oid_der, oid_len, d_hashes, d_sigs, d_pubkeys, n, d_codes, st);
-    if (l == 256) return launch_bign_verify_t<16>(oid_der, oid_len, d_hashes, d_sigs, d_pubkeys, n, d_codes, st);
-    return ERR_BAD_PARAMS;
+    return with_level(l, [&](auto N) { return launch_bign_verify_t<N()>(oid_der, oid_len, d_hashes, d_sigs, d_pubkeys, n, d_codes, st); });
 }
 
 // ---- one signer: the host's share ----------------------------------------------------------------------------------
@@ -1783,8 +1745,7 @@ unsigned long long bign_onekey_table_builds() { return g_keytab.n.builds.load();
 void set_onekey_slots(int v) { g_keytab.slots = v < 1 ? 1 : (size_t)v; }
 void set_onekey_tab16(int v) { g_keytab.tab16_log2 = v; }
 void drop_onekey_tables() { g_keytab.drop_all(); }
-static int g_onekey_quads = -1;                      // four lanes per signature: -1 by batch size (<= 2^16), 0 never, 1 always (tests / A/B: tune 22)
-void set_onekey_quads(int v) { g_onekey_quads = v; }
+void set_onekey_quads(int v) { g_force.onekey_quads = v; }   // four lanes per signature: -1 by batch size (<= 2^16), 0 never, 1 always (tests / A/B: tune 22)
 
 // The tables of nkeys keys (host memory, 2 NO octets each): out[k] = the cached entry, or null for a key without one.
 // n = signatures of this call under each key (counted towards the 16-bit table of a key when want16).
@@ -1866,49 +1827,23 @@ static err_t launch_bign_verify_onekey_t(const uint8_t *oid_der, size_t oid_len,
     OidArg oid;
     code = make_oid_arg(oid, oid_der, oid_len, st);
     if (code != ERR_OK) return code;
-    const unsigned g256 = (unsigned)((n + 255) / 256), g64 = (unsigned)((n + 63) / 64);
     const uint8_t *dh = (const uint8_t *)d_hashes, *dsg = (const uint8_t *)d_sigs;
-    // up to 2^16 signatures: four lanes per signature (a third of the latency; at 2^17 the one-lane kernels' two wavefronts per SIMD tie)
-    const bool quad = g_onekey_quads > 0 || (g_onekey_quads < 0 && n <= ((size_t)1 << 16));
-    const unsigned g4 = (unsigned)((4 * n + 255) / 256);
-    if (quad && keyed)
-        hipLaunchKernelGGL((bign_onekey4_kernel<N, VtOps, false, true>), dim3(g4), dim3(256), 0, st, dh, dsg, d_keys, n, S, (const uint4 *)gtab,
-                           (const uint4 *)nullptr, (const uint4 *)nullptr, (const uint32_t *)d_key_index, d_tabs, (uint32_t)nkeys);
-    else if (quad && tab16)
-        hipLaunchKernelGGL((bign_onekey4_kernel<N, VtOps, true, false>), dim3(g4), dim3(256), 0, st, dh, dsg, d_keys, n, S, (const uint4 *)gtab,
-                           tab, tab16, (const uint32_t *)nullptr, (const uint4 *const *)nullptr, 1u);
-    else if (quad)
-        hipLaunchKernelGGL((bign_onekey4_kernel<N, VtOps, false, false>), dim3(g4), dim3(256), 0, st, dh, dsg, d_keys, n, S, (const uint4 *)gtab,
-                           tab, (const uint4 *)nullptr, (const uint32_t *)nullptr, (const uint4 *const *)nullptr, 1u);
-    else if (keyed)
-        hipLaunchKernelGGL((bign_onekey_kernel<N, VtOps, false, true>), dim3(g256), dim3(256), 0, st, dh, dsg, d_keys, n, S, (const uint4 *)gtab,
-                           (const uint4 *)nullptr, (const uint4 *)nullptr, (const uint32_t *)d_key_index, d_tabs, (uint32_t)nkeys);
-    else if (tab16)
-        hipLaunchKernelGGL((bign_onekey_kernel<N, VtOps, true, false>), dim3(g256), dim3(256), 0, st, dh, dsg, d_keys, n, S, (const uint4 *)gtab,
-                           tab, tab16, (const uint32_t *)nullptr, (const uint4 *const *)nullptr, 1u);
+    const OnekeyPlan P = onekey_plan(N, n, keyed, tab16 != nullptr, g_force);
+    // the kernel's last two template arguments: the key's 16-bit table is read | keys and tables come through the key index
+    const auto walk = [&](auto kern_keyed, auto kern16, auto kern8, unsigned lanes) {
+        const auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)((lanes * n + 255) / 256)), dim3(256), 0, st, dh, dsg, d_keys, n, S, (const uint4 *)gtab, tab,
+                               tab16, (const uint32_t *)d_key_index, d_tabs, (uint32_t)nkeys);
+        };
+        if (keyed) go(kern_keyed);
+        else if (P.q16) go(kern16);
+        else go(kern8);
+    };
+    if (P.quad)
+        walk(bign_onekey4_kernel<N, VtOps, false, true>, bign_onekey4_kernel<N, VtOps, true, false>, bign_onekey4_kernel<N, VtOps, false, false>, 4);
     else
-        hipLaunchKernelGGL((bign_onekey_kernel<N, VtOps, false, false>), dim3(g256), dim3(256), 0, st, dh, dsg, d_keys, n, S, (const uint4 *)gtab,
-                           tab, (const uint4 *)nullptr, (const uint32_t *)nullptr, (const uint4 *const *)nullptr, 1u);
-    hipLaunchKernelGGL(bign_slow_kernel<N>, dim3(g64), dim3(64), 0, st, dsg, d_keys, n, S, keyed ? ~(size_t)0 : (size_t)0);
-    // shared inversions and the hash tail: as launch_bign_verify_t
-    // (round 4: with the division-step inversion the optimum is flat; up to 2^17 signatures on the 256-bit curve 2^16
-    //  lanes -- one wavefront per SIMD, two signatures each -- are 4-7 % ahead of 2^15; profiles/r04_inv_lanes_ab.txt)
-    const size_t inv_lanes = N == 8 && n > ((size_t)1 << 17) ? 32768 : 65536;
-    const size_t k_inv = std::min<size_t>(16, std::max<size_t>(1, n / inv_lanes));
-    const size_t lanes = (n + k_inv - 1) / k_inv;
-    hipLaunchKernelGGL(bign_inv_kernel<N>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, n, lanes, (int)k_inv, S);
-    constexpr size_t row_bytes = (2 * N + 1) * 4;
-    if (N == 8 && n >= 65536) {
-        auto kern = bign_tail_kernel<N, BeltTabTwoP, 1024>;
-        const size_t lds = BeltTabTwo::kBytes + 1024 * row_bytes;
-        B2H_TRY(dyn_lds_once(reinterpret_cast<const void *>(kern), lds));
-        hipLaunchKernelGGL(kern, dim3((unsigned)((n + 1023) / 1024)), dim3(1024), lds, st, dh, dsg, n, S, oid, (uint32_t *)d_codes);
-    } else {
-        hipLaunchKernelGGL((bign_tail_kernel<N, BeltTabSmall, 64>), dim3(g64), dim3(64), BeltTabSmall::kBytes + 64 * row_bytes, st,
-                           dh, dsg, n, S, oid, (uint32_t *)d_codes);
-    }
-    B2H_TRY(hipGetLastError());
-    return ERR_OK;
+        walk(bign_onekey_kernel<N, VtOps, false, true>, bign_onekey_kernel<N, VtOps, true, false>, bign_onekey_kernel<N, VtOps, false, false>, 1);
+    return verify_finish<N>(P.fin, dh, dsg, d_keys, keyed ? ~(size_t)0 : (size_t)0, n, S, oid, d_codes, st);
 }
 
 // n signatures under ONE public key of a standard curve; pubkey (2 NO octets) is HOST memory.  ERR_KEY_NOT_ON_CURVE: see common.hpp.
@@ -1917,11 +1852,8 @@ err_t launch_bign_verify_onekey(size_t l, const uint8_t *oid_der, size_t oid_len
 {
     if (n == 0) return ERR_OK;
     try {
-        if (l == 128) return launch_bign_verify_onekey_t<8>(oid_der, oid_len, d_hashes, d_sigs, pubkey, 1, nullptr, n, d_codes, st);
-        if (l == 192) return launch_bign_verify_onekey_t<12>(oid_der, oid_len, d_hashes, d_sigs, pubkey, 1, nullptr, n, d_codes, st);
-        if (l == 256) return launch_bign_verify_onekey_t<16>(oid_der, oid_len, d_hashes, d_sigs, pubkey, 1, nullptr, n, d_codes, st);
+        return with_level(l, [&](auto N) { return launch_bign_verify_onekey_t<N()>(oid_der, oid_len, d_hashes, d_sigs, pubkey, 1, nullptr, n, d_codes, st); });
     } catch (...) { return ERR_OUTOFMEMORY; }               // (bad_alloc, a thread that could not be started: nothing may leave the C ABI)
-    return ERR_BAD_PARAMS;
 }
 // n signatures of nkeys signers (pubkeys: HOST, nkeys x 2 NO octets; d_key_index: n x uint32 on the device)
 err_t launch_bign_verify_keyed(size_t l, const uint8_t *oid_der, size_t oid_len, const void *d_hashes, const void *d_sigs,
@@ -1930,11 +1862,8 @@ err_t launch_bign_verify_keyed(size_t l, const uint8_t *oid_der, size_t oid_len,
     if (n == 0) return ERR_OK;
     if (nkeys == 0 || !d_key_index) return ERR_BAD_INPUT;
     try {
-        if (l == 128) return launch_bign_verify_onekey_t<8>(oid_der, oid_len, d_hashes, d_sigs, pubkeys, nkeys, d_key_index, n, d_codes, st);
-        if (l == 192) return launch_bign_verify_onekey_t<12>(oid_der, oid_len, d_hashes, d_sigs, pubkeys, nkeys, d_key_index, n, d_codes, st);
-        if (l == 256) return launch_bign_verify_onekey_t<16>(oid_der, oid_len, d_hashes, d_sigs, pubkeys, nkeys, d_key_index, n, d_codes, st);
+        return with_level(l, [&](auto N) { return launch_bign_verify_onekey_t<N()>(oid_der, oid_len, d_hashes, d_sigs, pubkeys, nkeys, d_key_index, n, d_codes, st); });
     } catch (...) { return ERR_OUTOFMEMORY; }               // (bad_alloc, a thread that could not be started: nothing may leave the C ABI)
-    return ERR_BAD_PARAMS;
 }
 
 // the fallback of the one-key entries (a key off the curve, a non-standard parameter set): the key n times, then the general path
@@ -1958,12 +1887,11 @@ err_t launch_bign_pubkey_val(size_t l, const void *d_pubkeys, size_t n, void *d_
 {
     if (n == 0) return ERR_OK;
     const dim3 g((unsigned)((n + 255) / 256)), t(256);
-    if (l == 128) hipLaunchKernelGGL(bign_pubkey_val_kernel<8>, g, t, 0, st, (const uint8_t *)d_pubkeys, n, (uint32_t *)d_codes);
-    else if (l == 192) hipLaunchKernelGGL(bign_pubkey_val_kernel<12>, g, t, 0, st, (const uint8_t *)d_pubkeys, n, (uint32_t *)d_codes);
-    else if (l == 256) hipLaunchKernelGGL(bign_pubkey_val_kernel<16>, g, t, 0, st, (const uint8_t *)d_pubkeys, n, (uint32_t *)d_codes);
-    else return ERR_BAD_PARAMS;
-    B2H_TRY(hipGetLastError());
-    return ERR_OK;
+    return with_level(l, [&](auto N) -> err_t {
+        hipLaunchKernelGGL(bign_pubkey_val_kernel<N()>, g, t, 0, st, (const uint8_t *)d_pubkeys, n, (uint32_t *)d_codes);
+        B2H_TRY(hipGetLastError());
+        return ERR_OK;
+    });
 }
 
 #ifdef BEE2HIP_EXPERIMENTS
@@ -1971,12 +1899,11 @@ err_t launch_bign_debug_fe(size_t l, int op, const void *a, const void *b, void 
 {
     if (n == 0) return ERR_OK;
     const dim3 g((unsigned)((n + 63) / 64)), t(64);
-    if (l == 128) hipLaunchKernelGGL(bign_debug_fe_kernel<8>, g, t, 0, st, op, (const uint32_t *)a, (const uint32_t *)b, (uint32_t *)out, n);
-    else if (l == 192) hipLaunchKernelGGL(bign_debug_fe_kernel<12>, g, t, 0, st, op, (const uint32_t *)a, (const uint32_t *)b, (uint32_t *)out, n);
-    else if (l == 256) hipLaunchKernelGGL(bign_debug_fe_kernel<16>, g, t, 0, st, op, (const uint32_t *)a, (const uint32_t *)b, (uint32_t *)out, n);
-    else return ERR_BAD_PARAMS;
-    B2H_TRY(hipGetLastError());
-    return ERR_OK;
+    return with_level(l, [&](auto N) -> err_t {
+        hipLaunchKernelGGL(bign_debug_fe_kernel<N()>, g, t, 0, st, op, (const uint32_t *)a, (const uint32_t *)b, (uint32_t *)out, n);
+        B2H_TRY(hipGetLastError());
+        return ERR_OK;
+    });
 }
 #endif
 

@@ -36,6 +36,7 @@
 #include "bign_dev.hpp"
 #include "bign_fe29.hpp"
 #include "common.hpp"
+#include "bign_plan.hpp"
 
 namespace bee2hip {
 
@@ -1021,38 +1022,22 @@ static err_t sign_scratch(hipStream_t st, size_t n, SignScratch &S)
     return ERR_OK;
 }
 
-// k G by one lane per scalar (throughput) or by 64 / 16 / 4 lanes per scalar (latency; each form fills the device -- one
-// wavefront per SIMD -- at 2^10 / 2^12 / 2^14 scalars).  g_sign_lanes: 0 = by batch size; 1 = one lane (signed 6-bit windows,
-// Jacobian mixed additions), 4 / 16 / 64 = that many lanes, 8 = the LDS look-up form (256-bit curve; elsewhere by size) --
-// forced by bee2hip_internal_tune 10.  profiles/r03_sign_coop.txt measures the forms at every size on the three curves:
-// 64 lanes up to 2^10 scalars, 16 up to 2^13, 4 up to 2^15, one lane above.
-static int g_sign_lanes = 0;
-void set_sign_coop(int v) { g_sign_lanes = v; }
-// (round 4) 8 = one lane per scalar with the window's entry looked up in LDS (bign_mulbase_lds_kernel: 256-bit curve only,
-// signed 8-bit windows and 16 copies of the row): from 3 * 2^16 scalars on, where its one round of <= 256 workgroups (0.63 ms)
-// beats the scanning kernel's 256-lane blocks (0.55 ms at 2^17, 0.97 ms at 2^18: profiles/r04_sign_lds.txt)
-constexpr size_t MULBASE_LDS_MIN = (size_t)1 << 15, MULBASE_LDS_512_MAX = (size_t)1 << 17;   // (512-lane workgroups; round 6: from 2^15 scalars -- the 29-bit form with the shared inversion
-//  takes 0.27 | 0.35 ms (key | signature) for anything up to 2^17, the 4-lane cooperative form 0.35 | 0.43 ms at 2^15: profiles/r06_sign_l29_ab.txt)
-template <int N>
-static inline int mulbase_lanes(size_t n)
-{
-    if (g_sign_lanes == 1 || g_sign_lanes == 4 || g_sign_lanes == 16 || g_sign_lanes == 64) return g_sign_lanes;
-    if (N == 8 && (g_sign_lanes == 8 || (g_sign_lanes == 0 && n >= MULBASE_LDS_MIN))) return 8;
-    return n <= ((size_t)1 << 10) ? 64 : n <= ((size_t)1 << 13) ? 16 : n <= ((size_t)1 << 15) ? 4 : 1;
-}
+// Which form computes k G, and the workgroup of the hashing kernels: mulbase_plan and sign_wg of bign_plan.hpp.  g_force and MULBASE_LDS_BYTES are bign_kernels.hip's: this file sees them because bee2hip_tu_bign.hip includes that one first, as it does for the tables and WinW
+void set_sign_coop(int v) { g_force.sign_lanes = v; }
+static_assert(SIGN_WG_MIN == SIGN_WG && SIGN_TAB_BYTES == (size_t)BeltTabTwo::kBytes, "sign_wg() counts these lanes and this table");
 // the table the chosen form reads: the signed 8-bit one for form 8, the signed 6-bit one otherwise (`tab6` of launch_mulbase)
 template <int N>
-static err_t mulbase_tables(int lanes, const uint32_t **tab, const uint32_t **tabw, hipStream_t st)
+static err_t mulbase_tables(const MulbasePlan &P, const uint32_t **tab, const uint32_t **tabw, hipStream_t st)
 {
     err_t code = bign_table6<N>(tab, tabw, st);
-    if (code == ERR_OK && lanes == 8) {
-        if constexpr (N != 8) return ERR_BAD_INPUT;                      // (never: mulbase_lanes picks this form on the 256-bit curve only)
+    if (code == ERR_OK && P.lanes == 8) {
+        if constexpr (N != 8) return ERR_BAD_INPUT;                      // (never: mulbase_plan picks this form on the 256-bit curve only)
         else code = bign_tablew<N, 8>(tabw, st);
         if (code == ERR_OK) {
             static std::once_flag once[64];
             hipError_t e = hipSuccess;
             std::call_once(once[cur_dev() & 63], [&] {
-                const int bytes = (int)((size_t)WinW<8, 8>::ENT * 8 * 16 * 8);          // 128 entries x 64 octets x 16 copies
+                const int bytes = (int)MULBASE_LDS_BYTES<8>;
                 e = hipFuncSetAttribute(reinterpret_cast<const void *>(bign_mulbase_lds_kernel<8, 8, false>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
                 if (e == hipSuccess)
@@ -1064,62 +1049,46 @@ static err_t mulbase_tables(int lanes, const uint32_t **tab, const uint32_t **ta
     }
     return code;
 }
-// lanes: 64 / 16 / 4 = cooperative forms on the 4-bit windows of the seed table; 8 = the LDS look-up form; 1 = one lane per
-// scalar, signed 6-bit windows (tab6), Jacobian mixed additions
 template <int N, int MODE, bool X_ONLY>
-static void launch_mulbase(int lanes, const uint8_t *scalars, size_t n, uint32_t *codes, uint8_t *out, const uint32_t *tab,
+static void launch_mulbase(const MulbasePlan &P, const uint8_t *scalars, size_t n, uint32_t *codes, uint8_t *out, const uint32_t *tab,
                            const uint32_t *tab6, hipStream_t st)
 {
-    const dim3 g256((unsigned)((n + 255) / 256));
-    if (lanes == 64 || lanes == 16 || lanes == 4)
-        hipLaunchKernelGGL((bign_mulbase_coop_kernel<N>), dim3((unsigned)((n * (size_t)lanes + 63) / 64)), dim3(64), 0, st, scalars, n,
-                           codes, out, tab, MODE, (int)X_ONLY, lanes);
-    else if (lanes == 8) {
+    if (P.lanes == 64 || P.lanes == 16 || P.lanes == 4)
+        hipLaunchKernelGGL((bign_mulbase_coop_kernel<N>), dim3((unsigned)((n * (size_t)P.lanes + 63) / 64)), dim3(64), 0, st, scalars, n,
+                           codes, out, tab, MODE, (int)X_ONLY, P.lanes);
+    else if (P.lanes == 8) {
         // signed 8-bit windows, 16 copies of the row read with ds_read_b128 (tab6 = the 8-bit window table): 33 additions
         if constexpr (N == 8) {
-            constexpr size_t lds = (size_t)WinW<N, 8>::ENT * N * 8 * 16;
-            // up to 2^17 scalars: workgroups of 512 lanes (<= 256 of them: one per CU, two wavefronts per SIMD); above: 1024 lanes
-            if (n <= MULBASE_LDS_512_MAX)
-                hipLaunchKernelGGL((bign_mulbase_lds_kernel<N, 8, false, 512>), dim3((unsigned)((n + 511) / 512)), dim3(512), lds, st, scalars,
-                                   n, codes, out, reinterpret_cast<const uint64_t *>(tab6), MODE, (int)X_ONLY);
-            else
-                hipLaunchKernelGGL((bign_mulbase_lds_kernel<N, 8, false>), dim3((unsigned)((n + 1023) / 1024)), dim3(1024), lds, st, scalars, n,
+            const auto go = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3((unsigned)((n + P.wg - 1) / P.wg)), dim3((unsigned)P.wg), MULBASE_LDS_BYTES<N>, st, scalars, n,
                                    codes, out, reinterpret_cast<const uint64_t *>(tab6), MODE, (int)X_ONLY);
+            };
+            if (P.wg == 512) go(bign_mulbase_lds_kernel<N, 8, false, 512>);
+            else go(bign_mulbase_lds_kernel<N, 8, false>);
         }
     }
     else
-        hipLaunchKernelGGL((bign_mulbase_ct_kernel<N, 2>), g256, dim3(256), 0, st, scalars, n, codes, out, tab6, MODE, (int)X_ONLY);
+        hipLaunchKernelGGL((bign_mulbase_ct_kernel<N, 2>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, scalars, n, codes, out, tab6,
+                           MODE, (int)X_ONLY);
 }
 
 template <int N>
 static err_t launch_bign_pubkey_calc_t(bool keygen, const void *d_privkeys, size_t n, void *d_pubkeys, void *d_codes, hipStream_t st)
 {
     const uint32_t *tab = nullptr, *tab6 = nullptr;
-    const int lanes = mulbase_lanes<N>(n);
-    err_t code = mulbase_tables<N>(lanes, &tab, &tab6, st);
+    const MulbasePlan P = mulbase_plan(N, n, g_force);
+    err_t code = mulbase_tables<N>(P, &tab, &tab6, st);
     if (code != ERR_OK) return code;
     if (!keygen)
-        launch_mulbase<N, 1, false>(lanes, (const uint8_t *)d_privkeys, n, (uint32_t *)d_codes, (uint8_t *)d_pubkeys, tab, tab6, st);
+        launch_mulbase<N, 1, false>(P, (const uint8_t *)d_privkeys, n, (uint32_t *)d_codes, (uint8_t *)d_pubkeys, tab, tab6, st);
     else
-        launch_mulbase<N, 2, false>(lanes, (const uint8_t *)d_privkeys, n, (uint32_t *)d_codes, (uint8_t *)d_pubkeys, tab, tab6, st);
+        launch_mulbase<N, 2, false>(P, (const uint8_t *)d_privkeys, n, (uint32_t *)d_codes, (uint8_t *)d_pubkeys, tab, tab6, st);
     B2H_TRY(hipGetLastError());
     return ERR_OK;
 }
 
 // LDS row of the hashing kernels: the message zero-padded to whole 32-octet blocks, as an odd number of 32-bit words
 static inline uint32_t sign_row_words(size_t msg_octets) { return (uint32_t)((msg_octets + 31) / 32 * 8) | 1u; }
-// lanes per workgroup (one 64 KiB table each): big batches take the largest that fits the CU's 160 KiB with its rows
-// (256-bit curve, no t: 1024 lanes for the nonce, 512 for the tail -- 4 and 2 wavefronts per SIMD where it used to be 1)
-static inline int sign_wg(size_t n, uint32_t row_words)
-{
-    // ... as long as every CU still gets a workgroup: 2^16 signatures in 64 workgroups of 1024 lose 8 % (profiles/r03_sign_wg.txt)
-    if (n < ((size_t)1 << 17)) return SIGN_WG;
-    const int cap = n < ((size_t)1 << 18) ? 512 : 1024;
-    for (int wg = cap; wg > SIGN_WG; wg >>= 1)
-        if (BeltTabTwo::kBytes + (size_t)wg * row_words * 4 <= (size_t)160 * 1024) return wg;
-    return SIGN_WG;
-}
-
 // mode 0: deterministic (bignSign2): d_aux = t (n x t_len, or shared when t_shared), may be null
 // mode 1: one-time keys supplied (bignSign after its rng): d_aux = k, n x 4N octets
 // mode 2: deterministic with theta = belt-hash(oid || d || t) supplied: d_aux = n x 32 octets
@@ -1135,8 +1104,8 @@ static err_t launch_bign_sign_t(int mode, const uint8_t *oid_der, size_t oid_len
     err_t code = make_oid_arg(oa, oid_der, oid_len, st);
     if (code != ERR_OK) return code;
     const uint32_t *tab = nullptr, *tab6 = nullptr;
-    const int lanes = mulbase_lanes<N>(n);
-    code = mulbase_tables<N>(lanes, &tab, &tab6, st);
+    const MulbasePlan P = mulbase_plan(N, n, g_force);
+    code = mulbase_tables<N>(P, &tab, &tab6, st);
     if (code != ERR_OK) return code;
     SignScratch S;
     code = sign_scratch<N>(st, n, S);
@@ -1167,7 +1136,7 @@ static err_t launch_bign_sign_t(int mode, const uint8_t *oid_der, size_t oid_len
         B2H_TRY(hipMemcpyAsync(S.k, d_aux, n * 4 * N, hipMemcpyDeviceToDevice, st));
         kptr = S.k;
     }
-    launch_mulbase<N, 0, true>(lanes, kptr, n, (uint32_t *)nullptr, S.rx, tab, tab6, st);
+    launch_mulbase<N, 0, true>(P, kptr, n, (uint32_t *)nullptr, S.rx, tab, tab6, st);
     {
         const uint32_t rw = sign_row_words(oa.len + 8 * N);
         const int wg = sign_wg(n, rw);
@@ -1189,23 +1158,15 @@ static err_t launch_bign_sign_t(int mode, const uint8_t *oid_der, size_t oid_len
 err_t launch_bign_pubkey_calc(size_t l, bool keygen, const void *d_privkeys, size_t n, void *d_pubkeys, void *d_codes, hipStream_t st)
 {
     if (n == 0) return ERR_OK;
-    switch (l) {
-    case 128: return launch_bign_pubkey_calc_t<8>(keygen, d_privkeys, n, d_pubkeys, d_codes, st);
-    case 192: return launch_bign_pubkey_calc_t<12>(keygen, d_privkeys, n, d_pubkeys, d_codes, st);
-    case 256: return launch_bign_pubkey_calc_t<16>(keygen, d_privkeys, n, d_pubkeys, d_codes, st);
-    default: return ERR_BAD_PARAMS;
-    }
+    return with_level(l, [&](auto N) { return launch_bign_pubkey_calc_t<N()>(keygen, d_privkeys, n, d_pubkeys, d_codes, st); });
 }
 err_t launch_bign_sign(size_t l, int mode, const uint8_t *oid_der, size_t oid_len, const void *d_hashes,
                        const void *d_privkeys, const void *d_aux, size_t t_len, int t_shared, size_t n, void *d_sigs,
                        void *d_codes, hipStream_t st)
 {
-    switch (l) {
-    case 128: return launch_bign_sign_t<8>(mode, oid_der, oid_len, d_hashes, d_privkeys, d_aux, t_len, t_shared, n, d_sigs, d_codes, st);
-    case 192: return launch_bign_sign_t<12>(mode, oid_der, oid_len, d_hashes, d_privkeys, d_aux, t_len, t_shared, n, d_sigs, d_codes, st);
-    case 256: return launch_bign_sign_t<16>(mode, oid_der, oid_len, d_hashes, d_privkeys, d_aux, t_len, t_shared, n, d_sigs, d_codes, st);
-    default: return ERR_BAD_PARAMS;
-    }
+    return with_level(l, [&](auto N) {
+        return launch_bign_sign_t<N()>(mode, oid_der, oid_len, d_hashes, d_privkeys, d_aux, t_len, t_shared, n, d_sigs, d_codes, st);
+    });
 }
 
 }  // namespace bee2hip

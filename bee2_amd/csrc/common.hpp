@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
+#include <type_traits>
 #include "../../include/bee2hip.h"
 #ifdef BEE2HIP_EXPERIMENTS      // test / A/B hooks: only in libbee2hip_exp.so (bee2_amd/csrc/Makefile, target exp)
 #include "../../include/bee2hip_internal.h"
@@ -21,6 +22,16 @@ err_t hip_fail(hipError_t e, const char *what);
     } while (0)
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+
+// l = security level (128, 192, 256) -> f(std::integral_constant<int, N>), N = l / 16 32-bit words
+template <class F>
+static inline err_t with_level(size_t l, F &&f)
+{
+    if (l == 128) return f(std::integral_constant<int, 8>{});
+    if (l == 192) return f(std::integral_constant<int, 12>{});
+    if (l == 256) return f(std::integral_constant<int, 16>{});
+    return ERR_BAD_PARAMS;
+}
 
 // Library-owned device scratch, cached per (device, stream): two batches in flight on
 // different streams never share a buffer, two on the same stream are ordered by the stream.

@@ -608,7 +608,9 @@ def test_bign_pubkey_val_batch_and_dropin(orc, golden, l):
                                  (128, 32767), (128, 32768), (128, 65535), (128, 65536), (128, 2 ** 18 - 1), (128, 2 ** 18),
                                  # round 2: the quad kernel's workgroup switch (2^13) and the kernel switches at 2^15 / 2^16
                                  (128, 3), (128, 17), (128, 8191), (128, 8192), (128, 8193), (128, 16385), (128, 32769),
-                                 (128, 65537), (192, 8193), (192, 16384), (192, 16385), (256, 8192), (256, 16385)])
+                                 (128, 65537), (192, 8193), (192, 16384), (192, 16385), (256, 8192), (256, 16385),
+                                 # the helper form's one-wave blocks: 3 * 2^10 < n <= 2^12 (bign_plan.hpp)
+                                 (128, 3072), (128, 3073), (128, 4096), (128, 4097), (192, 3073), (192, 4097), (256, 4096)])
 def test_bign_shared_inversion_groups_with_mixed_statuses(golden, l, n):
     """bign_inv_kernel shares one inversion between K signatures (K = n / 32768 resp. n / 65536, here 2, 4 and 8)
     and from 2^18 signatures on bign_prep_kernel normalises the tables of two signatures with one inversion.
