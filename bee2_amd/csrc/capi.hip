@@ -16,6 +16,7 @@
 //   capi_beltae.hip belt-dwp / belt-che over ragged batches of records
 //   capi_fmt.hip    belt-fmt over batches of records, beltFMTEncr / beltFMTDecr
 //   capi_kwp.hip    belt-kwp over batches of keys of one length
+//   capi_hmac.hip   belt-hmac / belt-pbkdf2 over ragged batches, beltHMAC / beltPBKDF2
 //   capi_exp.hip    experiment hooks (libbee2hip_exp.so only)
 #include "staging.hpp"
 static const bool g_capture_query_set = (bee2hip::g_stream_capturing = bee2hip::stream_is_capturing, true);
@@ -28,4 +29,5 @@ static const bool g_capture_query_set = (bee2hip::g_stream_capturing = bee2hip::
 #include "capi_beltae.hip"
 #include "capi_fmt.hip"
 #include "capi_kwp.hip"
+#include "capi_hmac.hip"
 #include "capi_exp.hip"

@@ -363,29 +363,30 @@ void belt_mac_kernel(belt_mac_st *__restrict__ states, const uint8_t *__restrict
     }
 }
 
-// gather digests / tags of the generic batch path out of the per-item states
-__global__ void gather_results_kernel(const bash_hash_st *hs, const belt_mac_st *ms, size_t n,
-                                      size_t dlen, uint8_t *digests, uint8_t *tags)
+// The two ends of the generic batch path, one thread per item, in ONE kernel (a slot of the kernel inventory):
+// digests == tags == NULL initialises the per-item states, anything else gathers digests / tags out of them.  The direction is
+// a launch argument, read once; neither end is on a hot path.
+__global__ void mixed_states_kernel(bash_hash_st *hs, belt_mac_st *ms, size_t n, uint32_t level, MacKey key,
+                                    uint8_t *digests, uint8_t *tags)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (!digests && !tags) {
+        if (hs) {
+            for (int k = 0; k < 192; ++k) hs[i].s[k] = 0;
+            hs[i].s[184] = (uint8_t)(level / 4);
+            hs[i].buf_len = 192 - level / 2;
+            hs[i].pos = 0;
+        }
+        if (ms)
+            for (int k = 0; k < 8; ++k) ms[i].key[k] = key.k[k];
+        return;
+    }
+    const size_t dlen = level / 4;
     if (hs && digests)
         for (size_t k = 0; k < dlen; ++k) digests[i * dlen + k] = hs[i].s1[k];
     if (ms && tags)
         for (int k = 0; k < 8; ++k) tags[i * 8 + k] = (uint8_t)(ms[i].mac[k >> 2] >> (8 * (k & 3)));
-}
-__global__ void init_states_kernel(bash_hash_st *hs, belt_mac_st *ms, size_t n, uint32_t level, MacKey key)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (hs) {
-        for (int k = 0; k < 192; ++k) hs[i].s[k] = 0;
-        hs[i].s[184] = (uint8_t)(level / 4);
-        hs[i].buf_len = 192 - level / 2;
-        hs[i].pos = 0;
-    }
-    if (ms)
-        for (int k = 0; k < 8; ++k) ms[i].key[k] = key.k[k];
 }
 
 // ------------------------------------------------ 8f-3: ragged batches of messages ---
@@ -1010,14 +1011,15 @@ err_t launch_bashHash_beltMAC(const void *d_msgs, size_t msg_len, size_t n, size
     bash_hash_st *hs = (bash_hash_st *)base;
     belt_mac_st *ms = (belt_mac_st *)(hs + n);
     const unsigned g = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(init_states_kernel, dim3(g), dim3(256), 0, st, do_hash ? hs : nullptr,
-                       do_mac ? ms : nullptr, n, (uint32_t)l, k);
+    hipLaunchKernelGGL(mixed_states_kernel, dim3(g), dim3(256), 0, st, do_hash ? hs : nullptr,
+                       do_mac ? ms : nullptr, n, (uint32_t)l, k, (uint8_t *)nullptr, (uint8_t *)nullptr);
     err_t code = ERR_OK;
     if (do_hash) code = launch_bash_sponge(hs, d_msgs, msg_len, msg_len, n, 1, st);
     if (code == ERR_OK && do_mac) code = launch_belt_mac(ms, d_msgs, msg_len, msg_len, n, 1 | 2 | 4, st);
     if (code != ERR_OK) return code;
-    hipLaunchKernelGGL(gather_results_kernel, dim3(g), dim3(256), 0, st, do_hash ? hs : nullptr,
-                       do_mac ? ms : nullptr, n, l / 4, (uint8_t *)d_digests, (uint8_t *)d_tags);
+    hipLaunchKernelGGL(mixed_states_kernel, dim3(g), dim3(256), 0, st, do_hash ? hs : nullptr,
+                       do_mac ? ms : nullptr, n, (uint32_t)l, k, do_hash ? (uint8_t *)d_digests : nullptr,
+                       do_mac ? (uint8_t *)d_tags : nullptr);
     B2H_TRY(hipGetLastError());
     return ERR_OK;
 }

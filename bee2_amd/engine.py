@@ -71,7 +71,7 @@ DROPIN_SYMBOLS = [
     "beltCHEStepV", "beltCHEWrap", "beltCHEUnwrap",
     "beltMAC_keep", "beltMACStart", "beltMACStepA", "beltMACStepG", "beltMACStepG2",
     "beltMACStepV", "beltMACStepV2", "beltMAC",
-    "beltFMTEncr", "beltFMTDecr",
+    "beltFMTEncr", "beltFMTDecr", "beltHMAC", "beltPBKDF2",
     "bignParamsStd", "bignVerify", "bign128Verify", "bign192Verify", "bign256Verify",
     "bignPubkeyVal", "bign128PubkeyVal", "bign192PubkeyVal", "bign256PubkeyVal",
     "bignKeypairGen", "bignPubkeyCalc", "bignSign", "bignSign2",
@@ -103,6 +103,8 @@ BATCH_SYMBOLS = [
     "bee2hip_beltAE_wrap_ragged", "bee2hip_beltAE_unwrap_ragged", "bee2hip_beltAE_ragged_stream",
     "bee2hip_beltFMT_batch", "bee2hip_beltFMT_batch_stream",
     "bee2hip_beltKWP_wrap_batch", "bee2hip_beltKWP_unwrap_batch", "bee2hip_beltKWP_batch_stream",
+    "bee2hip_beltHMAC_ragged", "bee2hip_beltHMAC_verify_ragged", "bee2hip_beltHMAC_ragged_stream",
+    "bee2hip_beltPBKDF2_batch", "bee2hip_beltPBKDF2_batch_stream",
     "bee2hip_set_device", "bee2hip_sync", "bee2hip_last_error", "bee2hip_version", "bee2hip_path_policy", "bee2hip_path_count",
 ]
 # include/bee2hip_internal.h: test / bench hooks, not product ABI
@@ -407,6 +409,22 @@ class Engine:
             ctypes.c_int(unwrap), bytes(key), _sz(len(key)), self._optr(hdrs), self._optr(src), _sz(count), _sz(n),
             self._optr(dst), self._optr(codes), self._stream()), "beltKWP_batch_stream")
 
+    def beltHMAC_ragged_stream(self, verify, key, keys, key_offsets, data, offsets, order, n, macs, mac_len, codes=None):
+        """belt-hmac over n ragged messages: key (bytes: one key for the batch) or keys / key_offsets (device tensors: one key per
+        record), data (u8), offsets (int64, n + 1), order (int32, n, or None), macs (u8, n * mac_len: written, or compared when
+        verify) and codes (int32, n: verify only) are device tensors"""
+        self._check(self.lib.bee2hip_beltHMAC_ragged_stream(
+            ctypes.c_int(verify), None if key is None else bytes(key), _sz(0 if key is None else len(key)), self._optr(keys),
+            self._optr(key_offsets), self._optr(data), self._optr(offsets), self._optr(order), _sz(n), self._optr(macs),
+            _sz(mac_len), self._optr(codes), self._stream()), "beltHMAC_ragged_stream")
+
+    def beltPBKDF2_batch_stream(self, pwds, pwd_offsets, iters, salts, salt_len, salt_stride, order, n, keys):
+        """belt-pbkdf2 of n passwords (u8 / int64 offsets, n + 1): salt i = salts + i * salt_stride (0: one salt), salt_len octets;
+        keys (u8, 32 n); all device tensors, order (int32, n) or None"""
+        self._check(self.lib.bee2hip_beltPBKDF2_batch_stream(
+            self._optr(pwds), self._optr(pwd_offsets), _sz(iters), self._optr(salts), _sz(salt_len), _sz(salt_stride),
+            self._optr(order), _sz(n), self._optr(keys), self._stream()), "beltPBKDF2_batch_stream")
+
     def time_kernel(self, which, reps, a=None, b=None, c=None, d=None, n=0, aux=0):
         ms = ctypes.c_float(0)
         p = [self._ptr(t) if t is not None else None for t in (a, b, c, d)]
@@ -576,7 +594,61 @@ class Engine:
                                                      _sz(count), _sz(n), dst, codes)
         return code, dst.raw[:n * (count - 16)], list(codes)[:n]
 
+    def _hmac_keys(self, key):
+        """one key for the batch (bytes) or one per record (a list) -> (key, key_len, keys, key_offsets)"""
+        if isinstance(key, (bytes, bytearray)):
+            return bytes(key), _sz(len(key)), None, None
+        keys, koffs, _ = self._pack(key)
+        return None, _sz(0), keys, koffs
+
+    def beltHMAC_ragged(self, key, messages, mac_len=32):
+        """belt-hmac of every message: key = bytes (one key for the batch) or a list (one key per record)
+        -> (code, [mac_len octets per message])"""
+        n = len(messages)
+        data, offs, _ = self._pack(messages)
+        macs = ctypes.create_string_buffer(max(1, n * mac_len))
+        code = self.lib.bee2hip_beltHMAC_ragged(*self._hmac_keys(key), data, offs, _sz(n), macs, _sz(mac_len))
+        return code, [macs.raw[mac_len * i:mac_len * (i + 1)] for i in range(n)]
+
+    def beltHMAC_verify_ragged(self, key, messages, macs):
+        """macs: n strings of one length 1 .. 32 -> (code, [ERR_OK / ERR_BAD_MAC per record])"""
+        n = len(messages)
+        mac_len = len(macs[0]) if macs else 32
+        assert all(len(m) == mac_len for m in macs) and len(macs) == n
+        data, offs, _ = self._pack(messages)
+        codes = (_u32 * max(n, 1))()
+        code = self.lib.bee2hip_beltHMAC_verify_ragged(*self._hmac_keys(key), data, offs, _sz(n), b"".join(bytes(m) for m in macs),
+                                                       _sz(mac_len), codes)
+        return code, list(codes)[:n]
+
+    def beltPBKDF2_batch(self, pwds, iters, salts):
+        """belt-pbkdf2: pwds = a list of passwords; salts = bytes (one salt for the batch) or a list of n salts of one length
+        -> (code, [32-octet key per password])"""
+        n = len(pwds)
+        data, offs, _ = self._pack(pwds)
+        if isinstance(salts, (bytes, bytearray)):
+            salt, salt_len, stride = bytes(salts), len(salts), 0
+        else:
+            salt_len = len(salts[0]) if salts else 0
+            assert len(salts) == n and all(len(x) == salt_len for x in salts)
+            salt, stride = b"".join(bytes(x) for x in salts), salt_len
+        keys = ctypes.create_string_buffer(max(1, 32 * n))
+        code = self.lib.bee2hip_beltPBKDF2_batch(data, offs, _sz(iters), salt, _sz(salt_len), _sz(stride), _sz(n), keys)
+        return code, [keys.raw[32 * i:32 * i + 32] for i in range(n)]
+
     # ------------------------------------------------- bee2 drop-in interface
+    def beltHMAC(self, msg, key):
+        """-> (code, 32-octet MAC)"""
+        mac = ctypes.create_string_buffer(32)
+        code = self.lib.beltHMAC(mac, bytes(msg), _sz(len(msg)), bytes(key), _sz(len(key)))
+        return code, mac.raw
+
+    def beltPBKDF2(self, pwd, iters, salt):
+        """-> (code, 32-octet key)"""
+        key = ctypes.create_string_buffer(32)
+        code = self.lib.beltPBKDF2(key, bytes(pwd), _sz(len(pwd)), _sz(iters), bytes(salt), _sz(len(salt)))
+        return code, key.raw
+
     def beltFMT(self, decr, mod, symbols, key, iv=None):
         """beltFMTEncr / beltFMTDecr on a list of symbols -> (code, [symbols])"""
         n = len(symbols)

@@ -459,6 +459,52 @@ err_t bee2hip_beltKWP_unwrap_batch(const octet key[], size_t key_len, const octe
 err_t bee2hip_beltKWP_batch_stream(int unwrap, const octet key[], size_t key_len, const void *d_hdrs, const void *d_src,
                                    size_t count, size_t n, void *d_dst, void *d_codes, void *stream);
 
+/* ---- belt-hmac and belt-pbkdf2 over n records (STB 34.101.31; belt.h, src/crypto/belt/belt_hmac.c, belt_pbkdf.c) -------
+   Record by record these are bee2's one-shots
+       beltHMAC(mac_i, msg_i, len_i, key_i, key_len_i)  and  beltPBKDF2(key_i, pwd_i, pwd_len_i, iter, salt_i, salt_len).
+   One lane of belt_hmac_batch_kernel per record, whatever its length: long messages are NOT spread over several lanes.
+   Message i = data[offsets[i] .. offsets[i+1]) (n + 1 offsets).  The key comes in one of two forms: ONE key for the batch
+   (key != NULL, any key_len, keys and key_offsets NULL; its state is computed once on the host and travels in the launch
+   arguments), or one key per record (key NULL): key i = keys[key_offsets[i] .. key_offsets[i+1]).  A key of more than 32 octets
+   is belt-hashed first, as in bee2.  macs: mac_len (1 .. 32) octets a record, the first mac_len octets of the MAC, at
+   macs + i * mac_len.  verify: all mac_len octets of record i are compared (no early exit) and codes[i] becomes ERR_OK or
+   ERR_BAD_MAC; nothing else is written.
+   Before any device work: ERR_BAD_INPUT for a mac_len outside 1 .. 32, n >= 2^32, both key forms given, or with n > 0 neither
+   of them, decreasing offsets, or a NULL offsets, macs, codes (verify), data or keys that is needed; n = 0 is ERR_OK without
+   a device. */
+err_t bee2hip_beltHMAC_ragged(const octet key[], size_t key_len, const octet *keys, const uint64_t *key_offsets, const octet *data,
+                              const uint64_t *offsets, size_t n, octet *macs, size_t mac_len);
+err_t bee2hip_beltHMAC_verify_ragged(const octet key[], size_t key_len, const octet *keys, const uint64_t *key_offsets,
+                                     const octet *data, const uint64_t *offsets, size_t n, const octet *macs, size_t mac_len,
+                                     err_t *codes);
+/* The same on device pointers, asynchronous on `stream` (one queue, no fork; may be captured into a graph under the conditions
+   of bee2hip_beltAE_ragged_stream); verify = 0 or 1, anything else is ERR_BAD_INPUT.  The suffix is _stream for the reason
+   given at bee2hip_beltAE_ragged_stream; tests/test_gpu_belthmac.py holds the entry to the device-pointer contract.  key is a
+   HOST pointer (or NULL); d_keys, d_key_offsets, d_data, d_offsets are device pointers.  The offsets are 8-aligned, d_order
+   (NULL, or a permutation of 0 .. n - 1 as n x uint32: lane k serves record d_order[k]) and d_codes (n x err_t) 4-aligned, else
+   ERR_BAD_INPUT; data, keys and MACs need no alignment.  d_order NULL and n >= 128: the records are ordered by length on the
+   device.  verify = 1 reads d_macs and writes only d_codes; verify = 0 writes only the mac_len * n octets of d_macs.  The
+   offsets are not checked here. */
+err_t bee2hip_beltHMAC_ragged_stream(int verify, const octet key[], size_t key_len, const void *d_keys, const void *d_key_offsets,
+                                     const void *d_data, const void *d_offsets, const void *d_order, size_t n, void *d_macs,
+                                     size_t mac_len, void *d_codes, void *stream);
+/* PBKDF2: password i = pwds[pwd_offsets[i] .. pwd_offsets[i+1]); salt i = salts + i * salt_stride, salt_len octets
+   (salt_stride = 0: one salt for the batch); keys = 32 n octets.  ERR_BAD_INPUT for iter = 0 (as bee2), n >= 2^32, a salt_stride
+   that is neither 0 nor >= salt_len, decreasing offsets, a needed pointer that is NULL; ERR_NOT_IMPLEMENTED for iter above
+   2^17 = 131072: a launch's run time is proportional to iter, about 3 s at that count (beltPBKDF2 below has no such limit).  The stream form writes only the
+   32 n octets of d_keys; d_pwd_offsets is 8-aligned, d_order 4-aligned, nothing else needs alignment; with d_order NULL and
+   n >= 128 the records are ordered by password length. */
+err_t bee2hip_beltPBKDF2_batch(const octet *pwds, const uint64_t *pwd_offsets, size_t iter, const octet *salts, size_t salt_len,
+                               size_t salt_stride, size_t n, octet *keys);
+err_t bee2hip_beltPBKDF2_batch_stream(const void *d_pwds, const void *d_pwd_offsets, size_t iter, const void *d_salts,
+                                      size_t salt_len, size_t salt_stride, const void *d_order, size_t n, void *d_keys,
+                                      void *stream);
+/* bee2's one-shots (belt.h; codes as belt_hmac.c:244-263 and belt_pbkdf.c:31-36).  One record is one serial chain: it runs on
+   the host path unless the path policy is 1, which runs the kernel with n = 1; beltPBKDF2 with iter above 2^17 always runs on
+   the host.  bee2's step functions of belt-hmac are not exported. */
+err_t beltHMAC(octet mac[32], const void *src, size_t count, const octet key[], size_t len);
+err_t beltPBKDF2(octet key[32], const octet pwd[], size_t pwd_len, size_t iter, const octet salt[], size_t salt_len);
+
 /* ---- one host batch over several GPUs from one process --------------------------------
    The batch is cut into contiguous index ranges (bee2hip_multi_plan), one worker thread per device runs the
    single-device entry above on its range; no data crosses devices.  ndev = number of devices to use, 0 = all
