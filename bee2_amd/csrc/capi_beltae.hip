@@ -1,5 +1,5 @@
 // capi_beltae.hip -- belt-dwp / belt-che over ragged batches of records (STB 34.101.31; src/crypto/belt/belt_dwp.c, belt_che.c).
-// Part of the C ABI (capi.hip), after capi_prg.hip whose offset and ordering helpers it shares.  One record = one lane of
+// Part of the C ABI (capi.hip), after capi_prg.hip.  One record = one lane of
 // belt_ae_ragged_kernel (belt_ae_kernels.hip).  bee2's step functions stay what capi_belt.hip makes of them: one long stream.
 
 // what beltDWPWrap / beltCHEWrap refuse (belt_che.c:263) plus the limits of one launch; before any device work
@@ -38,8 +38,8 @@ try {
                                  as_stream(stream));
 } B2H_CATCH
 
-// ---- host-pointer entries, as prg_ae_host: stage through t_scr[3], the text once and processed in place, staged data keeps its
-// alignment mod 16, longest record first, one call of the stream entry on the NULL stream
+// ---- host-pointer entries, as prg_ae_host: stage through t_scr[3] (staging.hpp: the ragged part of a Stage), the text once and
+// processed in place, longest record first, one call of the stream entry on the NULL stream
 static err_t beltae_host(int unwrap, int mode, const octet key[], size_t key_len, const octet *ivs, const octet *hdrs,
                          const uint64_t *hdr_offsets, const octet *src, const uint64_t *offsets, size_t n, octet *dst, octet *tags,
                          err_t *codes)
@@ -48,34 +48,26 @@ static err_t beltae_host(int unwrap, int mode, const octet key[], size_t key_len
     if (code != ERR_OK) return code;
     if (n == 0) return ERR_OK;
     if (!offsets || !tags || !ivs || (unwrap && !codes) || (hdrs && !hdr_offsets)) return ERR_BAD_INPUT;
-    if (!prg_offsets_ok(offsets, n) || (hdr_offsets && !prg_offsets_ok(hdr_offsets, n))) return ERR_BAD_INPUT;
-    const size_t first = (size_t)offsets[0], total = (size_t)(offsets[n] - offsets[0]);
-    const size_t hfirst = hdr_offsets ? (size_t)hdr_offsets[0] : 0, htotal = hdr_offsets ? (size_t)(hdr_offsets[n] - hdr_offsets[0]) : 0;
-    if ((total && (!src || !dst)) || (htotal && !hdrs)) return ERR_BAD_INPUT;
-    std::vector<uint32_t> ord;
-    prg_longest_first(ord, offsets, n);
-    const size_t lead = first & 15, hlead = hfirst & 15;
+    if (!offsets_rise(offsets, n) || (hdr_offsets && !offsets_rise(hdr_offsets, n))) return ERR_BAD_INPUT;
     Stage sg(3, false, "bee2hip_beltAE staging");
-    const size_t o_txt = sg.add(lead + total), o_hdr = sg.add(hlead + htotal), o_iv = sg.add(n * 16), o_off = sg.add((n + 1) * 8),
-                 o_hoff = sg.add((n + 1) * 8), o_ord = sg.add(n * 4), o_tag = sg.add(n * 8), o_code = sg.add(n * 4);
+    RaggedPart txt(sg, offsets, n), hdr(sg, hdr_offsets, n);
+    if ((txt.total && (!src || !dst)) || (hdr.total && !hdrs)) return ERR_BAD_INPUT;
+    std::vector<uint32_t> ord;
+    longest_first(ord, offsets, n);
+    const size_t o_iv = sg.add(n * 16);
+    txt.add_offs(sg);
+    hdr.add_offs(sg);
+    const size_t o_ord = sg.add(n * 4), o_tag = sg.add(n * 8), o_code = sg.add(n * 4);
     B2H_OK(sg.open(16));
-    std::vector<uint64_t> off(n + 1);
-    for (size_t i = 0; i <= n; ++i) off[i] = offsets[i] - first + lead;
-    B2H_OK(sg.in(o_off, off.data(), (n + 1) * 8));
-    if (hdr_offsets) {
-        for (size_t i = 0; i <= n; ++i) off[i] = hdr_offsets[i] - hfirst + hlead;
-        B2H_OK(sg.in(o_hoff, off.data(), (n + 1) * 8));
-        if (htotal) B2H_OK(sg.in(o_hdr + hlead, hdrs + hfirst, htotal));
-    }
-    if (total) B2H_OK(sg.in(o_txt + lead, src + first, total));
+    B2H_OK(txt.in(sg, src));
+    B2H_OK(hdr.in(sg, hdrs));
     B2H_OK(sg.in(o_iv, ivs, n * 16));
     if (unwrap) B2H_OK(sg.in(o_tag, tags, n * 8));
     B2H_OK(sg.in(o_ord, ord.data(), n * 4));
     // in place on the device: the text is staged once
-    B2H_OK(bee2hip_beltAE_ragged_stream(unwrap, mode, key, key_len, sg.at(o_iv), hdr_offsets ? sg.at(o_hdr) : nullptr,
-                                        hdr_offsets ? sg.at(o_hoff) : nullptr, sg.at(o_txt), sg.at(o_off), sg.at(o_ord), n,
-                                        sg.at(o_txt), sg.at(o_tag), unwrap ? sg.at(o_code) : nullptr, nullptr));
-    if (total) B2H_OK(sg.out(dst + first, o_txt + lead, total));
+    B2H_OK(bee2hip_beltAE_ragged_stream(unwrap, mode, key, key_len, sg.at(o_iv), hdr.data(sg), hdr.offs(sg), txt.data(sg), txt.offs(sg),
+                                        sg.at(o_ord), n, txt.data(sg), sg.at(o_tag), unwrap ? sg.at(o_code) : nullptr, nullptr));
+    B2H_OK(txt.out(sg, dst));
     return unwrap ? sg.out(codes, o_code, n * 4) : sg.out(tags, o_tag, n * 8);
 }
 

@@ -71,7 +71,7 @@ try {
     return launch_belt_hmac_batch(A, d_pwds, d_pwd_offsets, d_salts, nullptr, d_order, n, d_keys, nullptr, as_stream(stream));
 } B2H_CATCH
 
-// ---- host-pointer entries, as beltae_host: one Stage, staged data keeps its alignment mod 16, longest record first, one call of
+// ---- host-pointer entries, as beltae_host: one Stage with its ragged parts (staging.hpp), longest record first, one call of
 // the stream entry on the NULL stream.  The keys are marked secret: their staging is zeroed when the Stage goes.
 static err_t belthmac_host(int verify, const octet key[], size_t key_len, const octet *keys, const uint64_t *key_offsets,
                            const octet *data, const uint64_t *offsets, size_t n, octet *macs, size_t mac_len, err_t *codes)
@@ -80,31 +80,22 @@ static err_t belthmac_host(int verify, const octet key[], size_t key_len, const 
     if (code != ERR_OK) return code;
     if (n == 0) return ERR_OK;
     if (!offsets || !macs || (verify && !codes) || (!key && !key_offsets)) return ERR_BAD_INPUT;
-    if (!prg_offsets_ok(offsets, n) || (key_offsets && !prg_offsets_ok(key_offsets, n))) return ERR_BAD_INPUT;
-    const size_t first = (size_t)offsets[0], total = (size_t)(offsets[n] - offsets[0]);
-    const size_t kfirst = key_offsets ? (size_t)key_offsets[0] : 0, ktotal = key_offsets ? (size_t)(key_offsets[n] - key_offsets[0]) : 0;
-    if ((total && !data) || (ktotal && !keys)) return ERR_BAD_INPUT;
-    std::vector<uint32_t> ord;
-    prg_longest_first(ord, offsets, n);
-    const size_t lead = first & 15, klead = kfirst & 15;
+    if (!offsets_rise(offsets, n) || (key_offsets && !offsets_rise(key_offsets, n))) return ERR_BAD_INPUT;
     Stage sg(3, false, "bee2hip_beltHMAC staging");
-    const size_t o_data = sg.add(lead + total), o_keys = sg.add(klead + ktotal), o_off = sg.add((n + 1) * 8),
-                 o_koff = sg.add((n + 1) * 8), o_ord = sg.add(n * 4), o_mac = sg.add(n * mac_len), o_code = sg.add(n * 4);
-    sg.secret(o_keys, klead + ktotal);
+    RaggedPart msg(sg, offsets, n), kys(sg, key_offsets, n);
+    if ((msg.total && !data) || (kys.total && !keys)) return ERR_BAD_INPUT;
+    std::vector<uint32_t> ord;
+    longest_first(ord, offsets, n);
+    msg.add_offs(sg);
+    kys.add_offs(sg);
+    const size_t o_ord = sg.add(n * 4), o_mac = sg.add(n * mac_len), o_code = sg.add(n * 4);
+    sg.secret(kys.o_data, kys.lead + kys.total);
     B2H_OK(sg.open(16));
-    std::vector<uint64_t> off(n + 1);
-    for (size_t i = 0; i <= n; ++i) off[i] = offsets[i] - first + lead;
-    B2H_OK(sg.in(o_off, off.data(), (n + 1) * 8));
-    if (key_offsets) {
-        for (size_t i = 0; i <= n; ++i) off[i] = key_offsets[i] - kfirst + klead;
-        B2H_OK(sg.in(o_koff, off.data(), (n + 1) * 8));
-        if (ktotal) B2H_OK(sg.in(o_keys + klead, keys + kfirst, ktotal));
-    }
-    if (total) B2H_OK(sg.in(o_data + lead, data + first, total));
+    B2H_OK(msg.in(sg, data));
+    B2H_OK(kys.in(sg, keys));
     if (verify) B2H_OK(sg.in(o_mac, macs, n * mac_len));
     B2H_OK(sg.in(o_ord, ord.data(), n * 4));
-    B2H_OK(bee2hip_beltHMAC_ragged_stream(verify, key, key_len, key_offsets ? sg.at(o_keys) : nullptr,
-                                          key_offsets ? sg.at(o_koff) : nullptr, sg.at(o_data), sg.at(o_off), sg.at(o_ord), n,
+    B2H_OK(bee2hip_beltHMAC_ragged_stream(verify, key, key_len, kys.data(sg), kys.offs(sg), msg.data(sg), msg.offs(sg), sg.at(o_ord), n,
                                           sg.at(o_mac), mac_len, verify ? sg.at(o_code) : nullptr, nullptr));
     return verify ? sg.out(codes, o_code, n * 4) : sg.out(macs, o_mac, n * mac_len);
 }
@@ -130,24 +121,22 @@ static err_t beltpbkdf2_host(const octet *pwds, const uint64_t *pwd_offsets, siz
     if (code != ERR_OK) return code;
     if (n == 0) return ERR_OK;
     if (!pwd_offsets || !keys || (salt_len && !salts)) return ERR_BAD_INPUT;
-    if (!prg_offsets_ok(pwd_offsets, n)) return ERR_BAD_INPUT;
-    const size_t first = (size_t)pwd_offsets[0], total = (size_t)(pwd_offsets[n] - pwd_offsets[0]);
-    if (total && !pwds) return ERR_BAD_INPUT;
-    std::vector<uint32_t> ord;
-    prg_longest_first(ord, pwd_offsets, n);
-    const size_t lead = first & 15, salt_bytes = (n - 1) * salt_stride + salt_len;
+    if (!offsets_rise(pwd_offsets, n)) return ERR_BAD_INPUT;
     Stage sg(3, false, "bee2hip_beltPBKDF2 staging");
-    const size_t o_pwd = sg.add(lead + total), o_key = sg.add(n * 32), o_salt = sg.add(salt_bytes), o_off = sg.add((n + 1) * 8),
-                 o_ord = sg.add(n * 4);
-    sg.secret(o_pwd, o_key + n * 32 - o_pwd);
+    RaggedPart pwd(sg, pwd_offsets, n);
+    if (pwd.total && !pwds) return ERR_BAD_INPUT;
+    std::vector<uint32_t> ord;
+    longest_first(ord, pwd_offsets, n);
+    const size_t salt_bytes = (n - 1) * salt_stride + salt_len;
+    const size_t o_key = sg.add(n * 32), o_salt = sg.add(salt_bytes);        // (the keys right behind the passwords: one secret range)
+    pwd.add_offs(sg);
+    const size_t o_ord = sg.add(n * 4);
+    sg.secret(pwd.o_data, o_key + n * 32 - pwd.o_data);
     B2H_OK(sg.open(16));
-    std::vector<uint64_t> off(n + 1);
-    for (size_t i = 0; i <= n; ++i) off[i] = pwd_offsets[i] - first + lead;
-    B2H_OK(sg.in(o_off, off.data(), (n + 1) * 8));
-    if (total) B2H_OK(sg.in(o_pwd + lead, pwds + first, total));
+    B2H_OK(pwd.in(sg, pwds));
     B2H_OK(sg.in(o_salt, salts, salt_bytes));
     B2H_OK(sg.in(o_ord, ord.data(), n * 4));
-    B2H_OK(bee2hip_beltPBKDF2_batch_stream(sg.at(o_pwd), sg.at(o_off), iter, sg.at(o_salt), salt_len, salt_stride, sg.at(o_ord), n,
+    B2H_OK(bee2hip_beltPBKDF2_batch_stream(pwd.data(sg), pwd.offs(sg), iter, sg.at(o_salt), salt_len, salt_stride, sg.at(o_ord), n,
                                            sg.at(o_key), nullptr));
     return sg.out(keys, o_key, n * 32);
 }

@@ -81,19 +81,14 @@ static err_t hash_ragged_host(size_t alg, const octet *data, const uint64_t *off
 {
     if (alg != 0 && alg != 128 && alg != 192 && alg != 256) return ERR_BAD_PARAMS;
     if (n == 0) return ERR_OK;
-    if (!offsets || !digests) return ERR_BAD_INPUT;
-    for (size_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i]) return ERR_BAD_INPUT;
+    if (!offsets || !digests || !offsets_rise(offsets, n)) return ERR_BAD_INPUT;
     const size_t total = (size_t)offsets[n] , dlen = alg ? alg / 4 : 32;
     if (total && !data) return ERR_BAD_INPUT;
     if (n > 0xffffffffull) return ERR_BAD_INPUT;
     // longest first: the 64 lanes of a wavefront then hold messages of similar length and the long
     // serial chains start at once (bench.py "hash_ragged": +20 % belt-hash, +57 % bash256)
-    std::vector<uint32_t> ord(n);
-    for (size_t i = 0; i < n; ++i) ord[i] = (uint32_t)i;
-    std::stable_sort(ord.begin(), ord.end(), [offsets](uint32_t a, uint32_t b) {
-        return offsets[a + 1] - offsets[a] > offsets[b + 1] - offsets[b];
-    });
+    std::vector<uint32_t> ord;
+    longest_first(ord, offsets, n);
     // A message is ONE dependent chain: a GPU lane (pair) walks it at ~0.12-0.15 us per octet, a host core at ~0.008.  When a
     // few messages are far longer than the rest the batch would wait for their chains (a 256 KiB message: 26-30 ms; a 1 GiB
     // file: minutes) with the device otherwise idle, so this HOST-pointer entry -- the data is in host memory anyway --

@@ -68,46 +68,27 @@ try {
                              as_stream(stream));
 } B2H_CATCH
 
-// ---- host-pointer entries: stage through t_scr[3], longest record first (a wavefront runs until its longest record is done),
-// one call of the stream entry on the NULL stream.  As hash_ragged_host without its host threads: a record's text has to come
-// back from wherever it was processed, so nothing is gained by keeping long ones here.
-static bool prg_offsets_ok(const uint64_t *offsets, size_t n)
-{
-    for (size_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i]) return false;
-    return true;
-}
-static void prg_longest_first(std::vector<uint32_t> &ord, const uint64_t *offsets, size_t n)
-{
-    ord.resize(n);
-    for (size_t i = 0; i < n; ++i) ord[i] = (uint32_t)i;
-    std::stable_sort(ord.begin(), ord.end(), [offsets](uint32_t a, uint32_t b) {
-        return offsets[a + 1] - offsets[a] > offsets[b + 1] - offsets[b];
-    });
-}
-
+// ---- host-pointer entries: stage through t_scr[3] (staging.hpp: the ragged part of a Stage), longest record first, one call of
+// the stream entry on the NULL stream.  As hash_ragged_host without its host threads: a record's text has to come back from
+// wherever it was processed, so nothing is gained by keeping long ones here.
 extern "C" err_t bee2hip_bashPrgHash_ragged(size_t l, size_t d, const octet ann[], size_t ann_len, const octet *data,
                                             const uint64_t *offsets, size_t n, octet *out, size_t out_len)
 try {
     err_t code = prg_check(l, d, ann, ann_len, false, nullptr, 0, out_len, n);
     if (code != ERR_OK) return code;
     if (n == 0) return ERR_OK;
-    if (!offsets || !out || !prg_offsets_ok(offsets, n)) return ERR_BAD_INPUT;
-    const size_t first = (size_t)offsets[0], total = (size_t)(offsets[n] - offsets[0]);
-    if (total && !data) return ERR_BAD_INPUT;
-    std::vector<uint32_t> ord;
-    prg_longest_first(ord, offsets, n);
-    // the data keeps its alignment mod 16 (first & 15 octets of slack in front), offsets are rebased to the staging block
-    const size_t lead = first & 15;
+    if (!offsets || !out || !offsets_rise(offsets, n)) return ERR_BAD_INPUT;
     Stage sg(3, false, "bee2hip_bashPrgHash_ragged staging");
-    const size_t o_data = sg.add(lead + total), o_off = sg.add((n + 1) * 8), o_ord = sg.add(n * 4), o_out = sg.add(n * out_len);
+    RaggedPart msg(sg, offsets, n);
+    if (msg.total && !data) return ERR_BAD_INPUT;
+    std::vector<uint32_t> ord;
+    longest_first(ord, offsets, n);
+    msg.add_offs(sg);
+    const size_t o_ord = sg.add(n * 4), o_out = sg.add(n * out_len);
     B2H_OK(sg.open(16));
-    std::vector<uint64_t> off(n + 1);
-    for (size_t i = 0; i <= n; ++i) off[i] = offsets[i] - first + lead;
-    if (total) B2H_OK(sg.in(o_data + lead, data + first, total));          // (data may be null when there is no text at all)
-    B2H_OK(sg.in(o_off, off.data(), (n + 1) * 8));
+    B2H_OK(msg.in(sg, data));
     B2H_OK(sg.in(o_ord, ord.data(), n * 4));
-    B2H_OK(bee2hip_bashPrgHash_ragged_stream(l, d, ann, ann_len, sg.at(o_data), sg.at(o_off), sg.at(o_ord), n, sg.at(o_out), out_len,
+    B2H_OK(bee2hip_bashPrgHash_ragged_stream(l, d, ann, ann_len, msg.data(sg), msg.offs(sg), sg.at(o_ord), n, sg.at(o_out), out_len,
                                              nullptr));
     return sg.out(out, o_out, n * out_len);
 } B2H_CATCH
@@ -120,34 +101,27 @@ static err_t prg_ae_host(int unwrap, size_t l, size_t d, const octet key[], size
     if (code != ERR_OK) return code;
     if (n == 0) return ERR_OK;
     if (!offsets || !tags || (ann_len && !anns) || (unwrap && !codes) || (hdrs && !hdr_offsets)) return ERR_BAD_INPUT;
-    if (!prg_offsets_ok(offsets, n) || (hdr_offsets && !prg_offsets_ok(hdr_offsets, n))) return ERR_BAD_INPUT;
-    const size_t first = (size_t)offsets[0], total = (size_t)(offsets[n] - offsets[0]);
-    const size_t hfirst = hdr_offsets ? (size_t)hdr_offsets[0] : 0, htotal = hdr_offsets ? (size_t)(hdr_offsets[n] - hdr_offsets[0]) : 0;
-    if ((total && (!src || !dst)) || (htotal && !hdrs)) return ERR_BAD_INPUT;
-    std::vector<uint32_t> ord;
-    prg_longest_first(ord, offsets, n);
-    const size_t lead = first & 15, hlead = hfirst & 15;
+    if (!offsets_rise(offsets, n) || (hdr_offsets && !offsets_rise(hdr_offsets, n))) return ERR_BAD_INPUT;
     Stage sg(3, false, "bee2hip_bashPrgAE staging");
-    const size_t o_txt = sg.add(lead + total), o_hdr = sg.add(hlead + htotal), o_ann = sg.add(n * ann_len), o_off = sg.add((n + 1) * 8),
-                 o_hoff = sg.add((n + 1) * 8), o_ord = sg.add(n * 4), o_tag = sg.add(n * tag_len), o_code = sg.add(n * 4);
+    RaggedPart txt(sg, offsets, n), hdr(sg, hdr_offsets, n);
+    if ((txt.total && (!src || !dst)) || (hdr.total && !hdrs)) return ERR_BAD_INPUT;
+    std::vector<uint32_t> ord;
+    longest_first(ord, offsets, n);
+    const size_t o_ann = sg.add(n * ann_len);
+    txt.add_offs(sg);
+    hdr.add_offs(sg);
+    const size_t o_ord = sg.add(n * 4), o_tag = sg.add(n * tag_len), o_code = sg.add(n * 4);
     B2H_OK(sg.open(16));
-    std::vector<uint64_t> off(n + 1);
-    for (size_t i = 0; i <= n; ++i) off[i] = offsets[i] - first + lead;
-    B2H_OK(sg.in(o_off, off.data(), (n + 1) * 8));
-    if (hdr_offsets) {
-        for (size_t i = 0; i <= n; ++i) off[i] = hdr_offsets[i] - hfirst + hlead;
-        B2H_OK(sg.in(o_hoff, off.data(), (n + 1) * 8));
-        if (htotal) B2H_OK(sg.in(o_hdr + hlead, hdrs + hfirst, htotal));
-    }
-    if (total) B2H_OK(sg.in(o_txt + lead, src + first, total));
+    B2H_OK(txt.in(sg, src));
+    B2H_OK(hdr.in(sg, hdrs));
     B2H_OK(sg.in(o_ann, anns, n * ann_len));
     if (unwrap) B2H_OK(sg.in(o_tag, tags, n * tag_len));
     B2H_OK(sg.in(o_ord, ord.data(), n * 4));
     // in place on the device: the text is staged once
-    B2H_OK(bee2hip_bashPrgAE_ragged_stream(unwrap, l, d, key, key_len, sg.at(o_ann), ann_len, hdr_offsets ? sg.at(o_hdr) : nullptr,
-                                           hdr_offsets ? sg.at(o_hoff) : nullptr, sg.at(o_txt), sg.at(o_off), sg.at(o_ord), n,
-                                           sg.at(o_txt), sg.at(o_tag), tag_len, unwrap ? sg.at(o_code) : nullptr, nullptr));
-    if (total) B2H_OK(sg.out(dst + first, o_txt + lead, total));
+    B2H_OK(bee2hip_bashPrgAE_ragged_stream(unwrap, l, d, key, key_len, sg.at(o_ann), ann_len, hdr.data(sg), hdr.offs(sg), txt.data(sg),
+                                           txt.offs(sg), sg.at(o_ord), n, txt.data(sg), sg.at(o_tag), tag_len,
+                                           unwrap ? sg.at(o_code) : nullptr, nullptr));
+    B2H_OK(txt.out(sg, dst));
     return unwrap ? sg.out(codes, o_code, n * 4) : sg.out(tags, o_tag, n * tag_len);
 }
 

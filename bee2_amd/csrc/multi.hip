@@ -286,9 +286,7 @@ extern "C" err_t bee2hip_hash_ragged_multi(size_t alg, const octet *data, const 
 try {
     if (alg != 0 && alg != 128 && alg != 192 && alg != 256) return ERR_BAD_PARAMS;
     if (n == 0) return ERR_OK;
-    if (!offsets || !digests) return ERR_BAD_INPUT;
-    for (size_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i]) return ERR_BAD_INPUT;
+    if (!offsets || !digests || !offsets_rise(offsets, n)) return ERR_BAD_INPUT;
     if (offsets[n] != offsets[0] && !data) return ERR_BAD_INPUT;
     const size_t dlen = alg ? alg / 4 : 32;
     int parts = ndev > 0 ? ndev : bee2hip_device_count();

@@ -341,6 +341,55 @@ public:
     }
 };
 
+// Ragged records: record i of n = octets [offsets[i], offsets[i + 1]) of one caller array.
+static inline bool offsets_rise(const uint64_t *offsets, size_t n)
+{
+    for (size_t i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i]) return false;
+    return true;
+}
+// the launch order of the one-lane-per-record kernels: a wavefront runs until its longest record is done (equal lengths keep
+// their index order)
+static inline void longest_first(std::vector<uint32_t> &ord, const uint64_t *offsets, size_t n)
+{
+    ord.resize(n);
+    for (size_t i = 0; i < n; ++i) ord[i] = (uint32_t)i;
+    std::stable_sort(ord.begin(), ord.end(), [offsets](uint32_t a, uint32_t b) {
+        return offsets[a + 1] - offsets[a] > offsets[b + 1] - offsets[b];
+    });
+}
+// The ragged part of a Stage: octets [offsets[0], offsets[n]) of a caller array and its n + 1 offsets (which rise: offsets_rise).
+// The staged octets keep their alignment mod 16 -- `lead` = first & 15 octets of nothing in front of them -- so the kernels see
+// the caller's own alignments, and the staged offsets are rebased to the staging block.  The kernels read the aligned 16-octet
+// quads that hold a record (bash_ragged_kernel): the entry asks open() for 16 octets of slack.  offsets == nullptr is an optional
+// array that is absent: nothing is staged and data() / offs() are null, which is what the stream entries take for "none".
+struct RaggedPart {
+    const uint64_t *const offsets;
+    const size_t n, first, total, lead;
+    size_t o_data = 0, o_off = 0;
+    // add()s the octets; the offsets are add()ed by add_offs(), wherever the entry's layout has them
+    RaggedPart(Stage &sg, const uint64_t *offsets_, size_t n_)
+        : offsets(offsets_), n(n_), first(offsets ? (size_t)offsets[0] : 0), total(offsets ? (size_t)(offsets[n] - offsets[0]) : 0),
+          lead(first & 15)
+    {
+        if (offsets) o_data = sg.add(lead + total);
+    }
+    void add_offs(Stage &sg) { if (offsets) o_off = sg.add((n + 1) * 8); }
+    // after open(): the rebased offsets, then the octets (src may be null when there are none)
+    err_t in(Stage &sg, const octet *src) const
+    {
+        if (!offsets) return ERR_OK;
+        std::vector<uint64_t> off(n + 1);
+        for (size_t i = 0; i <= n; ++i) off[i] = offsets[i] - (first - lead);
+        B2H_OK(sg.in(o_off, off.data(), (n + 1) * 8));
+        return total ? sg.in(o_data + lead, src + first, total) : ERR_OK;
+    }
+    // the octets back to dst[first, first + total): entries that work in place on the staged text
+    err_t out(Stage &sg, octet *dst) const { return total ? sg.out(dst + first, o_data + lead, total) : ERR_OK; }
+    octet *data(const Stage &sg) const { return offsets ? sg.at(o_data) : nullptr; }
+    octet *offs(const Stage &sg) const { return offsets ? sg.at(o_off) : nullptr; }
+};
+
 
 // ------------------------------------------------- host path for small single calls ---
 // host_small.hpp has the what and why.  Who runs where:

@@ -296,6 +296,87 @@ static void stage_helper()
     }
 }
 
+// ---- RaggedPart: the ragged part of a Stage, as the ragged host-pointer entries use it ----
+// n records cut out of a caller array from octet `first` on; the array carries a guard octet (and `first` octets nobody may
+// touch) in front and a guard behind.  lens has n entries.
+static void ragged_case(size_t first, const std::vector<size_t> &lens, bool device)
+{
+    const size_t n = lens.size();
+    std::vector<uint64_t> offs(n + 1);
+    offs[0] = first;
+    for (size_t i = 0; i < n; ++i) offs[i + 1] = offs[i] + lens[i];
+    const size_t total = (size_t)(offs[n] - offs[0]);
+    // caller's array: 16-aligned base, so that (data + first) mod 16 = first mod 16
+    std::vector<octet> raw(first + total + 1 + 16), back;
+    octet *data = raw.data() + ((16 - ((uintptr_t)raw.data() & 15)) & 15);
+    for (size_t i = 0; i < first + total + 1; ++i) data[i] = (octet)(i * 37 + 11 + n);
+    g_pinned_limit = device ? 0 : PINNED_MAX;
+    Stage sg(1, false, "ragged_part");
+    const size_t o_front = sg.add(5);                           // (something in front: the part starts at a later offset)
+    RaggedPart part(sg, offs.data(), n), none(sg, nullptr, n);
+    const size_t o_mid = sg.add(3);
+    part.add_offs(sg);
+    none.add_offs(sg);
+    const size_t o_end = sg.add(1);
+    CHECK(part.first == first && part.total == total && part.lead == (first & 15));
+    CHECK(part.o_data == up16(o_front + 5) && o_mid == up16(part.o_data + part.lead + total));
+    CHECK(part.o_off == up16(o_mid + 3) && o_end == up16(part.o_off + (n + 1) * 8));        // the absent part added nothing
+    CHECK(none.total == 0 && none.lead == 0);
+    CHECK(sg.open(16) == ERR_OK && in_pinned(sg.at(0)) == !device);
+    CHECK(none.data(sg) == nullptr && none.offs(sg) == nullptr);
+    CHECK(none.in(sg, nullptr) == ERR_OK && none.out(sg, nullptr) == ERR_OK);
+    CHECK(part.in(sg, total ? data : nullptr) == ERR_OK);       // no octets: a null array is accepted
+    // what was staged (read back through the runtime: the block may be "device" memory)
+    std::vector<octet> img(o_end + 1);
+    CHECK(hipMemcpy(img.data(), sg.at(0), img.size(), hipMemcpyDeviceToHost) == hipSuccess);
+    CHECK(part.data(sg) == sg.at(part.o_data) && part.offs(sg) == sg.at(part.o_off));
+    CHECK(((uintptr_t)sg.at(0) & 15) == 0);
+    CHECK(((uintptr_t)(part.data(sg) + part.lead) & 15) == ((uintptr_t)(data + first) & 15));
+    for (size_t i = 0; i < total; ++i) CHECK(img[part.o_data + part.lead + i] == data[first + i]);
+    for (size_t i = 0; i <= n; ++i) {
+        uint64_t v;
+        memcpy(&v, img.data() + part.o_off + 8 * i, 8);
+        CHECK(v == offs[i] - first + part.lead);
+    }
+    // out(): a "kernel" transforms the staged text in place; exactly [first, first + total) comes back
+    octet *txt = part.data(sg) + part.lead;
+    mockhipLaunch(nullptr, [=] { for (size_t i = 0; i < total; ++i) txt[i] = tf(txt[i], i); });
+    back.assign(1 + first + total + 1, 0xA5);
+    CHECK(part.out(sg, total ? back.data() + 1 : nullptr) == ERR_OK);
+    for (size_t i = 0; i < back.size(); ++i) {
+        const bool mine = i >= 1 + first && i < 1 + first + total;
+        CHECK(back[i] == (mine ? tf(data[i - 1], i - 1 - first) : 0xA5));
+    }
+    g_pinned_limit = PINNED_MAX;
+}
+static void ragged_part()
+{
+    for (int device = 0; device < 2; ++device) {
+        for (size_t first = 0; first <= 16; ++first) {
+            const size_t f = first < 16 ? first : 4099;
+            ragged_case(f, {0}, device);
+            ragged_case(f, {1}, device);
+            ragged_case(f, {33}, device);
+            ragged_case(f, {0, 0, 0}, device);
+            ragged_case(f, {5, 0, 16}, device);
+            ragged_case(f, {0, 31, 1}, device);
+        }
+    }
+    // offsets_rise: a descending pair is refused wherever it is
+    const uint64_t up[5] = {7, 7, 9, 20, 20}, d0[5] = {7, 6, 9, 20, 20}, dl[5] = {7, 7, 9, 20, 19}, d1[2] = {1, 0};
+    CHECK(offsets_rise(up, 4) && offsets_rise(up, 0) && !offsets_rise(d0, 4) && !offsets_rise(dl, 4) && !offsets_rise(d1, 1));
+    CHECK(offsets_rise(dl, 3));                                 // (only the first n + 1 offsets are looked at)
+    // longest_first: by decreasing length, equal lengths in index order
+    const uint64_t lo[8] = {0, 4, 4, 8, 20, 24, 24, 36};        // lengths 4 0 4 12 4 0 12
+    std::vector<uint32_t> ord(3, 99);
+    longest_first(ord, lo, 7);
+    const uint32_t want[7] = {3, 6, 0, 2, 4, 1, 5};
+    CHECK(ord.size() == 7);
+    for (size_t i = 0; i < 7; ++i) CHECK(ord[i] == want[i]);
+    longest_first(ord, lo, 0);
+    CHECK(ord.empty());
+}
+
 int main()
 {
     CHECK(ensure_device() == ERR_OK);
@@ -315,6 +396,7 @@ int main()
     }
     pool_and_fallback();
     stage_helper();
+    ragged_part();
     worker_pool();
     CHECK(hipDeviceSynchronize() == hipSuccess);
     puts("staging mock ok");
