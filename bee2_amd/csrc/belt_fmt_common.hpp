@@ -66,6 +66,25 @@ static inline size_t fmt_block_count(uint32_t mod, size_t n)
     return b ? b : 1;
 }
 
+// How a launch is cut.  A wavefront owns its numbers -- [limb][lane] dwords, 2 max(b1, b2) + 2 limbs -- and then its 64
+// records (128 count octets, 16-aligned); the S-box table sits in front of the wavefronts.  Four wavefronts per workgroup
+// while two workgroups fit a CU's 160 KiB, else two, else one (at b = 75, count = 600 one wavefront owns 38 KiB of numbers
+// and 75 KiB of records).
+constexpr uint32_t FMT_TAB_BYTES = 4096;        // BeltTabSmall
+struct FmtPlan { uint32_t b1, b2, num_bytes, wave_bytes, waves, lds; };
+static inline FmtPlan fmt_plan(uint32_t mod, size_t count)
+{
+    FmtPlan p;
+    p.b1 = (uint32_t)fmt_block_count(mod, (count + 1) / 2);
+    p.b2 = (uint32_t)fmt_block_count(mod, count / 2);
+    p.num_bytes = 256u * (2u * (p.b1 > p.b2 ? p.b1 : p.b2) + 2u);
+    p.wave_bytes = p.num_bytes + (uint32_t)(128 * count);
+    p.waves = 4;
+    while (p.waves > 1 && FMT_TAB_BYTES + p.waves * p.wave_bytes > 80u * 1024u) p.waves >>= 1;
+    p.lds = FMT_TAB_BYTES + p.waves * p.wave_bytes;
+    return p;
+}
+
 // floor(log2(mod)): every division by mod takes at least this many bits off the number (the uniform trip counts of the kernel
 // and the host path shrink with it)
 static inline uint32_t fmt_floor_log2(uint32_t mod)

@@ -234,9 +234,7 @@ void belt_fmt_batch_kernel(const BeltFmtArgs A, const uint8_t *__restrict__ ivs,
     }
 }
 
-// LDS of one wavefront: its numbers, then its records (16-aligned)
-static inline uint32_t fmt_num_bytes(size_t b1, size_t b2) { return 256u * (2u * (uint32_t)(b1 > b2 ? b1 : b2) + 2u); }
-static inline uint32_t fmt_wave_bytes(size_t count, size_t b1, size_t b2) { return fmt_num_bytes(b1, b2) + (uint32_t)(128 * count); }
+static_assert(FmtTab::kBytes == FMT_TAB_BYTES, "fmt_plan() counts the table the kernel fills");
 
 // key: expanded; H: the S-box octets (host); d_ivs may be null (all zero)
 err_t launch_belt_fmt_batch(int decr, uint32_t mod, size_t count, const uint32_t key[8], const uint8_t *H, const void *d_ivs,
@@ -256,19 +254,14 @@ err_t launch_belt_fmt_batch(int decr, uint32_t mod, size_t count, const uint32_t
     A.count = (uint32_t)count;
     A.n1 = (uint32_t)((count + 1) / 2);
     A.n2 = (uint32_t)(count / 2);
-    const size_t b1 = fmt_block_count(mod, A.n1), b2 = fmt_block_count(mod, A.n2);
-    A.b1 = (uint32_t)b1;
-    A.b2 = (uint32_t)b2;
-    A.num_bytes = fmt_num_bytes(b1, b2);
-    A.wave_bytes = fmt_wave_bytes(count, b1, b2);
-    // four wavefronts per workgroup while two workgroups fit a CU's 160 KiB, else two, else one (at b = 75, count = 600 one
-    // wavefront owns 38 KiB of numbers and 75 KiB of records)
-    unsigned waves = 4;
-    while (waves > 1 && FmtTab::kBytes + waves * (size_t)A.wave_bytes > 80 * 1024) waves >>= 1;
-    const size_t lds = FmtTab::kBytes + waves * (size_t)A.wave_bytes;
-    B2H_TRY(dyn_lds_once(reinterpret_cast<const void *>(belt_fmt_batch_kernel), lds));
-    const size_t per_wg = 64 * (size_t)waves;
-    hipLaunchKernelGGL(belt_fmt_batch_kernel, dim3((unsigned)((n + per_wg - 1) / per_wg)), dim3(64 * waves), lds, st, A,
+    const FmtPlan P = fmt_plan(mod, count);                              // (belt_fmt_common.hpp: 4, 2 or 1 wavefronts)
+    A.b1 = P.b1;
+    A.b2 = P.b2;
+    A.num_bytes = P.num_bytes;
+    A.wave_bytes = P.wave_bytes;
+    B2H_TRY(dyn_lds_once(reinterpret_cast<const void *>(belt_fmt_batch_kernel), P.lds));
+    const size_t per_wg = 64 * (size_t)P.waves;
+    hipLaunchKernelGGL(belt_fmt_batch_kernel, dim3((unsigned)((n + per_wg - 1) / per_wg)), dim3(64 * P.waves), P.lds, st, A,
                        (const uint8_t *)d_ivs, (const uint16_t *)d_src, n, (uint16_t *)d_dst);
     B2H_TRY(hipGetLastError());
     return ERR_OK;

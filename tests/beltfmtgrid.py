@@ -25,6 +25,50 @@ SMALL = [s for s in ALL_SHAPES if max(blocks(*s)) <= 4]
 LARGE = [s for s in ALL_SHAPES if max(blocks(*s)) > 4]
 
 
+# ---- the launch plan: fmt_plan() of belt_fmt_common.hpp restated (tests/test_beltfmt.py holds the two together)
+TAB_BYTES, WG_LDS_MAX = 4096, 80 * 1024
+
+
+def plan(mod, count):
+    """-> (waves, lds): a wavefront owns 256 (2 max(b1, b2) + 2) octets of numbers and 128 count of records; 4, 2 or 1
+    wavefronts per workgroup, as many as keep the workgroup within 80 KiB"""
+    wave_bytes = 256 * (2 * max(blocks(mod, count)) + 2) + 128 * count
+    waves = 4
+    while waves > 1 and TAB_BYTES + waves * wave_bytes > WG_LDS_MAX:
+        waves //= 2
+    return waves, TAB_BYTES + waves * wave_bytes
+
+
+# mod: (the last count with 4 wavefronts, the last count with 2): the plan changes form behind each
+SEAMS = {2: (140, 288), 10: (132, 268), 58: (124, 252), 257: (116, 238), 65535: (96, 200), 65536: (96, 200)}
+# both sides of both seams; at (2, 140), (10, 132), (257, 116) four wavefronts take exactly 80 KiB, at (2, 288), (65535, 200)
+# and (65536, 200) two do
+PLAN_SHAPES = [(mod, c + d) for mod in (2, 10, 257, 65535, 65536) for c in SEAMS[mod] for d in (0, 1)]
+
+
+def plan_n(mod, count):
+    """the batch size of a seam shape: a second workgroup starts with one record; one started second wavefront where the
+    model is slow (the small moduli: many symbols per number)"""
+    return 65 if mod in (2, 257) else 64 * plan(mod, count)[0] + 1
+
+
+# ---- every block count 1..40, on the 2^16 path (65536) and on the division path (65535): at count 8 b - 7 the larger half
+# has b blocks and the smaller b - 1, so consecutive steps of a record alternate between two limb counts, L = 2 b + 2 = 0 and
+# 2 mod 4.  And 1..16 at modulus 10, the smallest count whose larger half has b blocks: many divisions per limb.
+SWEEP_B = range(1, 41)
+
+
+def _sweep(b):
+    out = [(65536, max(2, 8 * b - 7)), (65535, max(2, 8 * b - 7))]
+    if b <= 16:
+        out.append((10, next(c for c in range(2, M.COUNT_MAX + 1) if M.block_count(10, (c + 1) // 2) == b)))
+    return out
+
+
+SWEEP = {b: _sweep(b) for b in SWEEP_B}
+SWEEP_SHAPES = [s for b in SWEEP_B for s in SWEEP[b]]
+
+
 def symbols(rnd, mod, count, oor):
     """count symbols below mod; with oor (and a modulus that leaves room) one to three of them at or above it"""
     s = [rnd.randrange(mod) for _ in range(count)]
@@ -42,6 +86,12 @@ def fixture_cases():
             for decr in (0, 1):
                 out.append({"mod": mod, "count": count, "key_len": key_len, "decr": decr, "iv": (j + k + decr) % 3 != 0,
                             "oor": (j + 2 * k + decr) % 4 == 1, "seed": 7000000 + 1000 * j + 10 * k + decr})
+    # the seam shapes, appended (a row's seed comes from its index): one key length each, both directions
+    for j, (mod, count) in enumerate(PLAN_SHAPES, len(ALL_SHAPES)):
+        k = j % 3
+        for decr in (0, 1):
+            out.append({"mod": mod, "count": count, "key_len": KEY_LENS[k], "decr": decr, "iv": (j + k + decr) % 3 != 0,
+                        "oor": (j + 2 * k + decr) % 4 == 1, "seed": 7000000 + 1000 * j + 10 * k + decr})
     return out
 
 

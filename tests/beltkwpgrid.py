@@ -9,12 +9,24 @@ import random
 import orc_beltkwp as M
 
 KEY_LENS = (16, 24, 32)
-FIXTURE_COUNTS = list(range(16, 100)) + [127, 128, 129, 1007, 1008]
+FIXTURE_COUNTS = list(range(16, 100)) + [127, 128, 129, 1007, 1008] + [288, 289, 592, 593]       # (append only: seeds come from the index)
 # the shapes of the GPU batches: T = 32 (the sum is r1 alone); every tail residue mod 4; a dword tail that is not a multiple
 # of 8; T = 40 (8 mod 16); around the A.21 shape; around four whole blocks; T = 256
 GPU_COUNTS = [16, 17, 18, 19, 20, 24, 31, 32, 33, 47, 48, 49, 240]
 GPU_COUNTS_CAP = [1007, 1008]                                      # one wavefront per workgroup
 BATCH_SIZES = (1, 63, 64, 65, 257)
+# both sides of the two changes of the launch plan: T = 303..306 (four wavefronts up to 304, then two) and 607..610 (two up to
+# 608, then one); T = 304 and 608 are whole dwords, the others take the octet path
+SEAM_COUNTS = [287, 288, 289, 290, 591, 592, 593, 594]
+
+
+def plan(T):
+    """kwp_plan() of belt_kwp_common.hpp restated -> (waves, lds); tests/test_beltkwp.py holds the two together"""
+    wave_bytes = 256 * ((T + 3) // 4)
+    waves = 4
+    while waves > 1 and 4096 + waves * wave_bytes > 80 * 1024:
+        waves //= 2
+    return waves, 4096 + waves * wave_bytes
 
 
 # ---- the committed fixture (tools/make_golden_beltkwp.py writes it from the reference): a row's inputs come from its seed

@@ -40,6 +40,12 @@ void hf_crypt(int decr, uint32_t mod, size_t count, const uint32_t key[8], const
     fmt_crypt(g_T, decr, mod, count, key, g_H, iv, buf);
 }
 size_t hf_block_count(uint32_t mod, size_t n) { return fmt_block_count(mod, n); }
+// the launch plan of belt_fmt_batch_kernel: b1, b2, num_bytes, wave_bytes, waves, lds
+void hf_plan(uint32_t mod, size_t count, uint32_t out[6])
+{
+    const FmtPlan p = fmt_plan(mod, count);
+    out[0] = p.b1; out[1] = p.b2; out[2] = p.num_bytes; out[3] = p.wave_bytes; out[4] = p.waves; out[5] = p.lds;
+}
 // every rem < mod and every h < 2^16
 uint64_t hf_div_exhaustive(uint32_t mod)
 {

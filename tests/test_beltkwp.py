@@ -31,7 +31,8 @@ def fixture():
 def test_fixture_covers_every_count_key_length_and_header_form(fixture):
     rows = fixture["rows"]
     assert [{k: r[k] for k in ("count", "key_len", "header", "seed")} for r in rows] == G.fixture_cases()
-    assert {r["count"] for r in rows} == set(range(16, 100)) | {127, 128, 129, 1007, 1008}
+    assert {r["count"] for r in rows} == set(range(16, 100)) | {127, 128, 129, 1007, 1008} | {288, 289, 592, 593}
+    assert G.FIXTURE_COUNTS[-4:] == [288, 289, 592, 593] and set(G.FIXTURE_COUNTS[-4:]) <= set(G.SEAM_COUNTS)
     for count in G.FIXTURE_COUNTS:
         mine = [r for r in rows if r["count"] == count]
         assert {(r["key_len"], r["header"]) for r in mine} == {(k, h) for k in G.KEY_LENS for h in (True, False)}
@@ -149,8 +150,13 @@ def test_slab_layout_and_launch_plan(hk):
         assert wave_bytes == 256 * -(-T // 4) and lds == 4096 + waves * wave_bytes
         assert waves in (1, 2, 4) and lds <= 80 * 1024
         assert waves == 4 or 4096 + 2 * waves * wave_bytes > 80 * 1024
+        assert (waves, lds) == G.plan(T)                          # the restatement the GPU seam tests compute their plans with
+        assert waves == (4 if T <= 304 else 2 if T <= 608 else 1)
         seen.add(waves)
     assert seen == {1, 2, 4} and waves == 1 and lds == 4096 + 65536
+    # the seam counts of the GPU tests sit on both sides of both changes, and reach the 80 KiB launch of either form
+    plans = [G.plan(c + 16) for c in G.SEAM_COUNTS]
+    assert [w for w, _ in plans] == [4, 4, 2, 2, 2, 2, 1, 1] and {w for w, lds in plans if lds == 81920} == {2, 4}
 
 
 # ================================================================================================ the interface

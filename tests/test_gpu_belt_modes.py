@@ -92,18 +92,25 @@ def test_modes_blocks_dev_vs_oracle(orc, golden, nblocks):
     assert host(dst) == orc.cbc(data, key, iv, True)[1]
 
 
-def test_cbc_encr_batch_lane_per_message(orc, golden):
+@pytest.mark.parametrize("n", [1, 65, 1025])
+@pytest.mark.parametrize("nblk", [1, 7, 8, 9, 16, 17])
+def test_cbc_encr_batch_lane_per_message(orc, golden, nblk, n):
+    """the kernel walks a message eight blocks at a time and the rest block by block: the tail alone at its shortest and
+    longest, the unrolled loop alone once and twice, and both with a tail of one; one lane, a started second wavefront, a
+    started second workgroup.  Every message and every chaining value against the oracle, and the block behind the messages and
+    behind the ivs left as it was"""
     eng = engine()
     key = golden.H[128:160]
     kw = bytes(orc.key_expand(key))
-    n, nblk = 300, 17
-    msgs = orc.fill(n * nblk * 16, 5)
-    ivs = orc.fill(n * 16, 6)
+    size = n * nblk * 16
+    msgs = orc.fill(size + 16, 5 + 100 * nblk + n)
+    ivs = orc.fill(n * 16 + 16, 6 + 100 * nblk + n)
     dm, di = dev(msgs), dev(ivs)
-    eng.beltCBCEncr_batch_dev(dm, nblk, kw, di)
+    eng.beltCBCEncr_batch_dev(dm[:size], nblk, kw, di[:16 * n])
     torch.cuda.synchronize()
     out, chain = host(dm), host(di)
-    for m in (0, 1, 63, 64, 299):
+    assert out[size:] == msgs[size:] and chain[16 * n:] == ivs[16 * n:]
+    for m in range(n):
         want = orc.cbc(msgs[m * nblk * 16:(m + 1) * nblk * 16], key, ivs[16 * m: 16 * m + 16])[1]
-        assert out[m * nblk * 16:(m + 1) * nblk * 16] == want
-        assert chain[16 * m: 16 * m + 16] == want[-16:]
+        assert out[m * nblk * 16:(m + 1) * nblk * 16] == want, m
+        assert chain[16 * m: 16 * m + 16] == want[-16:], m

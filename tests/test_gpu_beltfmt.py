@@ -128,6 +128,34 @@ def test_large_shapes(shape):
     check(engine(), G.batch(shape[0], shape[1], 65, G.KEY_LENS[G.LARGE.index(shape) % 3]))
 
 
+@pytest.mark.parametrize("shape", G.PLAN_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_both_sides_of_both_seams_of_the_launch_plan(shape):
+    """the launcher picks 4, 2 or 1 wavefronts per workgroup from the LDS a wavefront needs (fmt_plan, belt_fmt_common.hpp):
+    the last count of one form and the first of the next, at five moduli -- the 2-wavefront form, the 4- and 2-wavefront forms
+    at exactly 80 KiB, the 1-wavefront form at its smallest.  n starts a second workgroup with one record (65 at the two
+    moduli where the model is slow: a second wavefront).  Key lengths and iv / NULL iv rotate.  The plans are recomputed
+    here, so that a retuned rule fails this test instead of leaving a form unlaunched"""
+    plans = [G.plan(*s) for s in G.PLAN_SHAPES]
+    assert {w for w, _ in plans} == {1, 2, 4} and any(lds == 81920 for _, lds in plans)
+    assert {w for w, lds in plans if lds == 81920} == {2, 4}
+    j = G.PLAN_SHAPES.index(shape)
+    waves, lds = plans[j]
+    n = G.plan_n(*shape)
+    assert n in (65, 64 * waves + 1) and lds <= 80 * 1024
+    check(engine(), G.batch(shape[0], shape[1], n, G.KEY_LENS[j % 3], ivs=j % 4 != 3))
+
+
+@pytest.mark.parametrize("b", G.SWEEP_B)
+def test_every_block_count_on_both_number_paths(b):
+    """the trip counts of the kernel's Horner conversion, of its belt-wbl walk over 2 b + 2 limbs and of its shrinking division
+    all come from b: every b = 1..40 with modulus 65536 (the number is the symbols) and 65535 (multiplication and division),
+    at a count whose halves have b and b - 1 blocks, and b = 1..16 at modulus 10 (many divisions per limb); n = 65"""
+    eng = engine()
+    for j, (mod, count) in enumerate(G.SWEEP[b]):
+        assert max(G.blocks(mod, count)) == b
+        check(eng, G.batch(mod, count, 65, G.KEY_LENS[(b + j) % 3], ivs=(b + j) % 4 != 3))
+
+
 @pytest.mark.parametrize("key_len", G.KEY_LENS)
 @pytest.mark.parametrize("ivs", [True, False], ids=["ivs", "null-ivs"])
 def test_every_key_length_with_and_without_ivs(key_len, ivs):

@@ -138,6 +138,27 @@ def test_counts_at_the_cap(count):
     check(engine(), G.batch(count, 65, G.KEY_LENS[count % 3]))
 
 
+@pytest.mark.parametrize("count", G.SEAM_COUNTS)
+def test_both_sides_of_both_seams_of_the_launch_plan(count):
+    """the launcher picks 4, 2 or 1 wavefronts per workgroup from T (kwp_plan, belt_kwp_common.hpp): T = 303..306 and 607..610
+    -- the last two sizes of one form and the first two of the next, among them the 2-wavefront form, which no other test
+    launches, and T = 304 and 608, whose four and two wavefronts take exactly 80 KiB.  Wrap, and unwrap with every fifth
+    record refused; n = 65 with headers and n = 64 waves + 1 (a second workgroup starts with one record) with NULL headers;
+    src and dst 4-aligned (whole dwords at T = 304 and 608) and at 1 and 3 mod 4 (octets).  The plans are recomputed here, so
+    that a retuned rule fails this test instead of leaving a form unlaunched"""
+    plans = [G.plan(c + 16) for c in G.SEAM_COUNTS]
+    assert {w for w, _ in plans} == {1, 2, 4} and {w for w, lds in plans if lds == 81920} == {2, 4}
+    waves, lds = G.plan(count + 16)
+    assert lds <= 80 * 1024
+    eng = engine()
+    j = G.SEAM_COUNTS.index(count)
+    for n, hdrs in ((65, True), (64 * waves + 1, False)):
+        b = G.batch(count, n, G.KEY_LENS[(j + n) % 3], seed=11, hdrs=hdrs, refuse=True)
+        assert b.refused == list(range(2, n, 5)) and [i for i, c in enumerate(b.want_unwrap()[1]) if c] == b.refused
+        for src_off, dst_off in ((0, 0), (1, 3)):
+            check(eng, b, src_off=src_off, dst_off=dst_off)
+
+
 def test_the_published_vector_inside_a_batch():
     """STB 34.101.31 A.21 as record 1 of 3 and A.22 as record 1 of 3"""
     eng, H = engine(), orclib.Golden().H

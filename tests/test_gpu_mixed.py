@@ -20,8 +20,11 @@ def _check(eng, orc, key, msg_len, n, l, want_hash=True, want_mac=True, seed=1):
 
 
 @pytest.mark.parametrize("l", [128, 192, 256])
-@pytest.mark.parametrize("msg_len", [0, 16, 48, 64, 80, 96, 128, 192, 256, 1024, 4096, 4096 + 48])
+@pytest.mark.parametrize("msg_len", [0, 16, 48, 64, 80, 96, 128, 192, 256, 1024, 4096, 4096 + 48,
+                                     32, 112, 240, 4096 + 32, 4096 + 112])
 def test_fused_kernel_shapes(orc, golden, l, msg_len):
+    """(the last five lengths: at l = 128 a rate block is 8 blocks of 16 octets, and these leave 2, 7, 7, 2 and 7 of them --
+    at 7 the padding word sits in the rate block's last slot)"""
     eng = engine()
     _check(eng, orc, golden.H[128:160], msg_len, 67, l)
 

@@ -2,8 +2,9 @@
 beltFMTEncr / beltFMTDecr / beltFMT_keep, src/crypto/belt/belt_fmt.c).  Build container only.
 
   * "rows": tests/beltfmtgrid.py fixture_cases() -- every shape x key lengths 16 / 24 / 32 x both directions, some without iv,
-    some with symbols at or above the modulus; inputs come from each row's seed, outputs as hex (sha256 above 64 symbols),
-    with the block counts b1 / b2 the reference uses for the two halves;
+    some with symbols at or above the modulus, then the seam shapes of the launch plan (PLAN_SHAPES) with one key length each;
+    inputs come from each row's seed, outputs as hex (sha256 above 64 symbols), with the block counts b1 / b2 the reference
+    uses for the two halves;
   * "blocks": [mod, n, b] for beltfmtgrid.block_pairs(), read off beltFMT_keep (its state ends in 8 (b(mod, n1) + 1) octets).
 The script decrypts every encrypted in-range row with the reference again and stops on a difference."""
 import ctypes

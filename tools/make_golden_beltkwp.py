@@ -1,7 +1,7 @@
 """tests/golden/belt_kwp.json: belt-kwp rows with the reference's own outputs (oracle/_ref/libbee2ref.so: beltKWPWrap /
 beltKWPUnwrap, src/crypto/belt/belt_kwp.c).  Build container only.
 
-  * "rows": tests/beltkwpgrid.py fixture_cases() -- wrap counts 16..99, 127, 128, 129, 1007, 1008 x key lengths 16 / 24 / 32 x
+  * "rows": tests/beltkwpgrid.py fixture_cases() -- wrap counts 16..99, 127, 128, 129, 1007, 1008, 288, 289, 592, 593 x key lengths 16 / 24 / 32 x
     with and without header; inputs come from each row's seed.  Per row: the token; code and output of unwrapping the token
     with one bit flipped; code and output of unwrapping the token under a wrong header.  Outputs as hex (sha256 above 64
     octets).
