@@ -156,6 +156,29 @@ def test_sign_with_given_one_time_keys_against_the_oracle(hc, orc, l):
 
 
 @pytest.mark.parametrize("l", [128, 192, 256])
+def test_sign_with_steered_keys_on_the_reference_fixture(hc, l):
+    """tests/golden/bign_sign_tail.json (tests/signtail.py): private keys solved so that (s0 + 2^l) d mod q is 1, cq - 1, cq, q - 1 and
+    the rest -- mod_q's final masked subtraction taken and not taken --, k - r is 0 and q - 1, u - H is 0 and q - 1, and H >= q
+    with and without a residue coming out of sub_mod_q.  The reference's octets, every record, the "wrap" ones included."""
+    import signtail as T
+    q = _curve_q(l)
+    recs = T.load().of(l)
+    assert {c["kind"] for c in recs} == set(T.KINDS)
+    taken = 0
+    for c in recs:
+        sig = ctypes.create_string_buffer(3 * l // 8)
+        assert hc.hc_sign(_sz(l), c["oid"], _sz(len(c["oid"])), c["hash"], c["priv"], c["k"], None, _sz(0), sig) == 0
+        assert sig.raw == c["sig"], (c["kind"], c["name"])
+        r = T.record_tail(c, q)["r"]
+        taken += r < 2 ** (2 * l) - q
+        n = l // 4                                   # mod_q itself on this record's product: r, below cq or not
+        out = ctypes.create_string_buffer(n)
+        hc.hc_mod_q(_sz(l), out, T.product(l, T.le(c["sig"][:l // 8]), T.le(c["priv"])).to_bytes(2 * n, "little"))
+        assert int.from_bytes(out.raw, "little") == r, (c["kind"], c["name"])
+    assert taken >= 3
+
+
+@pytest.mark.parametrize("l", [128, 192, 256])
 def test_sign2_random_against_the_oracle(hc, orc, l):
     from bee2_amd import engine as E
     no, sg = l // 4, 3 * l // 8

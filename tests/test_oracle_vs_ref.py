@@ -3,6 +3,7 @@
 inputs.  Skipped where _ref is absent.  tests/pin_oracle.py runs the same comparison at
 >= 1e5 items per primitive."""
 import ctypes
+import json
 import os
 import random
 
@@ -276,6 +277,26 @@ def test_sign2_pubkey_calc_random(orc):
             want = ctypes.create_string_buffer(sg)
             assert getattr(L, f"bign{l}Sign2")(want, h, priv, t, _sz(t_len)) == 0
             assert orc.sign2(l, oid[l], h, priv, t) == (0, want.raw), (l, t_len)
+
+
+@pytest.mark.parametrize("seed", [0x7A12, 0x7A13, 0x7A14])
+def test_steered_signing_tails_from_fresh_seeds(orc, seed):
+    """the kinds of tests/golden/bign_sign_tail.json drawn anew by the tool's generator (tools/make_golden_sign_tail.py: the final
+    subtraction of the fold, every reachable event of it, u = 0 / q - 1, s1 = 0 / q - 1, H >= q with and without a residue coming
+    out): the oracle's signature, public key and verdict against the live reference's, other k, H, c and keys than the fixture's"""
+    import make_golden_sign_tail as MT
+    import signtail as T
+    assert seed != MT.SEED
+    recs = MT.build(seed)
+    fixture = {(r["l"], r["kind"], r["name"]): r for r in json.load(open(T.PATH))["records"]}
+    assert sorted((r["l"], r["kind"], r["name"]) for r in recs) == sorted(fixture)
+    for r in recs:
+        what = (r["l"], r["kind"], r["name"])
+        assert r["k"] != fixture[what]["k"] or r["hash"] != fixture[what]["hash"], what
+        oid, d, k, h, sig, pub = (bytes.fromhex(r[f]) for f in ("oid", "priv", "k", "hash", "sig", "pub"))
+        assert orc.sign_rnd(r["l"], oid, h, d, k) == (0, sig, 1), what
+        assert orc.pubkey_calc(r["l"], d) == (0, pub), what
+        assert orc.verify_l(r["l"], oid, h, sig, pub) == r["verify"] == (510 if r["kind"] == "wrap" else 0), what
 
 
 def test_generic_parameter_fixtures_are_what_the_reference_says():
