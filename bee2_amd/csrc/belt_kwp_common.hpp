@@ -40,6 +40,24 @@ B2H_HD static inline uint32_t kwp_slab_octet(uint32_t T, uint32_t l, uint32_t b)
     return ((q >> 2) * 64u + l) * 4u + (q & 3u);
 }
 
+// A record's own key: key_len = 16, 24 or 32 octets at q, any alignment, read octet by octet -> the eight words that
+// beltKeyExpand2 makes of them (belt_lcl.c: 16 octets are repeated; 24 get k6 = k0 ^ k1 ^ k2 and k7 = k3 ^ k4 ^ k5).  key_len is
+// uniform over a batch: no branch and no address depends on a key octet.
+B2H_HD static inline void kwp_key_words(uint32_t (&K)[8], const uint8_t *q, uint32_t key_len)
+{
+    const uint32_t words = key_len >> 2;
+B2H_UNROLL
+    for (uint32_t k = 0; k < 8; ++k)
+        K[k] = k < words ? (uint32_t)q[4 * k] | (uint32_t)q[4 * k + 1] << 8 | (uint32_t)q[4 * k + 2] << 16 | (uint32_t)q[4 * k + 3] << 24 : 0u;
+    if (key_len == 16) {
+B2H_UNROLL
+        for (uint32_t k = 0; k < 4; ++k) K[4 + k] = K[k];
+    } else if (key_len == 24) {
+        K[6] = K[0] ^ K[1] ^ K[2];
+        K[7] = K[3] ^ K[4] ^ K[5];
+    }
+}
+
 // dword `lo` and the one above it, moved down by sh = 0, 8, 16 or 24 bits (v_alignbit_b32 on the device)
 B2H_HD static inline uint32_t kwp_funnel(uint32_t lo, uint32_t hi, uint32_t sh)
 {

@@ -1,6 +1,7 @@
 // belt_kwp_kernels.hip -- belt-kwp (STB 34.101.31, key wrap; src/crypto/belt/belt_kwp.c = belt-wbl over key || header) over a
-// batch of records that share the length and the key, one record per lane.  Device side of bee2hip_beltKWP_*batch*
-// (capi_kwp.hip).  Part of bee2hip_tu_belt.hip, after belt_kernels.hip (BeltKey, dyn_lds_once).
+// batch of records that share the length, one record per lane, under one key for the batch or one key per record.  Device
+// side of bee2hip_beltKWP_*batch* (capi_kwp.hip) and of the bpki containers (capi_bpki.hip).  Part of bee2hip_tu_belt.hip, after
+// belt_kernels.hip (BeltKey, dyn_lds_once).
 #pragma once
 #include "belt_dev.hpp"
 #include "belt_kwp_common.hpp"
@@ -33,10 +34,16 @@ struct KwpEK {
 // The 64 records of a wavefront are 64 in_len contiguous octets of global memory: they come in as whole rows of consecutive
 // octets -- dwords when the base is 4-aligned and the length a multiple of 4 -- and are transposed on the way into the slab;
 // results go out the same way, only the records' own octets, so that a partial last wavefront touches nothing behind them.
+//
+// Two instantiations.  KEYED = false is the batch under one key, whose expanded words travel in `key` and stay in scalar
+// registers: its text is what it was before the keyed form came (the two arguments behind `codes` are not looked at).  KEYED =
+// true takes one key per record from `keys` (DESIGN.md 4.17 says why it is not one kernel with a null test).
+template <bool KEYED>
 __global__ __launch_bounds__(KWP_WG_MAX)
 void belt_kwp_batch_kernel(const BeltKey key, const uint32_t T, const uint32_t unwrap, const uint32_t wave_bytes,
                            const uint8_t *__restrict__ hdrs, const uint8_t *__restrict__ src, const size_t n,
-                           uint8_t *__restrict__ dst, uint32_t *__restrict__ codes)
+                           uint8_t *__restrict__ dst, uint32_t *__restrict__ codes, const uint8_t *__restrict__ keys,
+                           const uint32_t key_len)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     KwpTab::fill(smem, threadIdx.x, blockDim.x);
@@ -84,12 +91,21 @@ B2H_ROLLED
         for (int k = 0; k < 4; ++k)
             hdr[k] = (uint32_t)q[4 * k] | (uint32_t)q[4 * k + 1] << 8 | (uint32_t)q[4 * k + 2] << 16 | (uint32_t)q[4 * k + 3] << 24;
     }
+    // KEYED: the key_len octets of record g0 + lane, read as the header is and expanded by kwp_key_words() (belt_kwp_common.hpp:
+    // the tests run it on the CPU).  Lanes past nrec take the zero key
+    uint32_t K[8];
+    if (KEYED) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) K[k] = 0u;
+        if (lane < nrec) kwp_key_words(K, keys + (size_t)key_len * (g0 + lane), key_len);
+    }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
 
-    uint32_t K[8];
+    if (!KEYED) {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) K[k] = key.k[k];
+        for (int k = 0; k < 8; ++k) K[k] = key.k[k];
+    }
     KwpColumn col{slab + lane};
     KwpEK ek{Tab, K};
     const uint32_t code = kwp_lane(col, ek, T, unwrap, hdr);             // (lanes past nrec work on what the slab held: LDS only)
@@ -125,22 +141,24 @@ B2H_ROLLED
     }
 }
 
-// key: expanded; count: the octets of a record of src (the key to wrap, or the token); d_hdrs may be null (all zero);
-// d_codes: unwrap only
-err_t launch_belt_kwp_batch(int unwrap, size_t count, const uint32_t key[8], const void *d_hdrs, const void *d_src, size_t n,
-                            void *d_dst, void *d_codes, hipStream_t st)
+// key: expanded, for the whole batch, or null with d_keys: n keys of key_len = 16, 24 or 32 octets, any alignment; count: the
+// octets of a record of src (the key to wrap, or the token); d_hdrs may be null (all zero); d_codes: unwrap only
+err_t launch_belt_kwp_batch(int unwrap, size_t count, const uint32_t key[8], const void *d_keys, size_t key_len, const void *d_hdrs,
+                            const void *d_src, size_t n, void *d_dst, void *d_codes, hipStream_t st)
 {
     if (n == 0) return ERR_OK;
     const size_t T = unwrap ? count : count + 16;
     if (n > 0xffffffffull || T < KWP_TOKEN_MIN || T > KWP_TOKEN_MAX || (unwrap && !d_codes)) return ERR_BAD_INPUT;
+    if (!key == !d_keys || (d_keys && key_len != 16 && key_len != 24 && key_len != 32)) return ERR_BAD_INPUT;
     BeltKey k;
-    for (int i = 0; i < 8; ++i) k.k[i] = key[i];
+    for (int i = 0; i < 8; ++i) k.k[i] = key ? key[i] : 0u;
     const KwpPlan plan = kwp_plan((uint32_t)T);
-    B2H_TRY(dyn_lds_once(reinterpret_cast<const void *>(belt_kwp_batch_kernel), plan.lds));
+    const auto kern = d_keys ? belt_kwp_batch_kernel<true> : belt_kwp_batch_kernel<false>;
+    B2H_TRY(dyn_lds_once(reinterpret_cast<const void *>(kern), plan.lds));
     const size_t per_wg = 64 * (size_t)plan.waves;
-    hipLaunchKernelGGL(belt_kwp_batch_kernel, dim3((unsigned)((n + per_wg - 1) / per_wg)), dim3(64 * plan.waves), plan.lds, st, k,
-                       (uint32_t)T, unwrap ? 1u : 0u, plan.wave_bytes, (const uint8_t *)d_hdrs, (const uint8_t *)d_src, n,
-                       (uint8_t *)d_dst, (uint32_t *)d_codes);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((n + per_wg - 1) / per_wg)), dim3(64 * plan.waves), plan.lds, st, k, (uint32_t)T,
+                       unwrap ? 1u : 0u, plan.wave_bytes, (const uint8_t *)d_hdrs, (const uint8_t *)d_src, n, (uint8_t *)d_dst,
+                       (uint32_t *)d_codes, (const uint8_t *)d_keys, (uint32_t)key_len);
     B2H_TRY(hipGetLastError());
     return ERR_OK;
 }

@@ -17,6 +17,7 @@
 //   capi_fmt.hip    belt-fmt over batches of records, beltFMTEncr / beltFMTDecr
 //   capi_kwp.hip    belt-kwp over batches of keys of one length
 //   capi_hmac.hip   belt-hmac / belt-pbkdf2 over ragged batches, beltHMAC / beltPBKDF2
+//   capi_bpki.hip   bpki password containers: PBKDF2 into a per-record-key belt-kwp, DER frames on the host
 //   capi_exp.hip    experiment hooks (libbee2hip_exp.so only)
 #include "staging.hpp"
 static const bool g_capture_query_set = (bee2hip::g_stream_capturing = bee2hip::stream_is_capturing, true);
@@ -30,4 +31,5 @@ static const bool g_capture_query_set = (bee2hip::g_stream_capturing = bee2hip::
 #include "capi_fmt.hip"
 #include "capi_kwp.hip"
 #include "capi_hmac.hip"
+#include "capi_bpki.hip"
 #include "capi_exp.hip"

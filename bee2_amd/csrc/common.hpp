@@ -82,9 +82,10 @@ err_t launch_belt_che(const void *d_src, void *d_dst, size_t nblocks, const uint
                       uint64_t first, void *d_s_out, hipStream_t st);
 err_t launch_belt_fmt_batch(int decr, uint32_t mod, size_t count, const uint32_t key[8], const uint8_t *H, const void *d_ivs,
                             const void *d_src, size_t n, void *d_dst, hipStream_t st);
-// count: the octets of a record of src (wrap: the key, unwrap: the token); d_hdrs may be null; d_codes: unwrap only
-err_t launch_belt_kwp_batch(int unwrap, size_t count, const uint32_t key[8], const void *d_hdrs, const void *d_src, size_t n,
-                            void *d_dst, void *d_codes, hipStream_t st);
+// count: the octets of a record of src (wrap: the key, unwrap: the token); key (expanded, one for the batch) or d_keys (n keys of
+// key_len octets on the device), not both; d_hdrs may be null; d_codes: unwrap only
+err_t launch_belt_kwp_batch(int unwrap, size_t count, const uint32_t key[8], const void *d_keys, size_t key_len, const void *d_hdrs,
+                            const void *d_src, size_t n, void *d_dst, void *d_codes, hipStream_t st);
 // belt-hmac / belt-pbkdf2 (belt_hmac_kernels.hip): launch_belt_hmac_batch takes the kernel's own HmacArgs and is declared there
 err_t launch_belt_polyhash(const void *d_data, size_t nbytes, const uint32_t r[4], const uint32_t t[4],
                            void *d_t_out, hipStream_t st);

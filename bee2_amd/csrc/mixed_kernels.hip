@@ -788,24 +788,25 @@ void belt_hash_long_kernel(const uint8_t *__restrict__ data, const uint64_t *__r
 __device__ __forceinline__ unsigned ragged_bucket(uint64_t len) { return len ? 63u - (unsigned)__builtin_clzll(len) + 1u : 0u; }
 // (global atomics of 65 536 threads on ~19 addresses serialise -- 160 us per kernel; a workgroup therefore
 // counts in LDS first and touches each global bucket once)
+// One kernel, launched twice (the phase is an argument, uniform over the launch; the LDS arrays are shared):
+//   phase 0, the histogram: work[b] += this workgroup's count of bucket b;
+//   phase 1, the scatter.  Where a bucket starts = how many messages the longer buckets hold: a suffix sum over the 64 counts,
+//   which the first wavefront of every workgroup takes for itself in six shuffle steps.
+// (They were ragged_hist_kernel and ragged_scatter_kernel; the slot went to the keyed form of belt_kwp_batch_kernel)
 __global__ __launch_bounds__(256)
-void ragged_hist_kernel(const uint64_t *__restrict__ off, size_t n, unsigned *__restrict__ work)
-{
-    __shared__ unsigned h[64];
-    if (threadIdx.x < 64) h[threadIdx.x] = 0;
-    __syncthreads();
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) atomicAdd(&h[ragged_bucket(off[i + 1] - off[i])], 1u);
-    __syncthreads();
-    if (threadIdx.x < 64 && h[threadIdx.x]) atomicAdd(&work[threadIdx.x], h[threadIdx.x]);
-}
-// Where a bucket starts = how many messages the longer buckets hold: a suffix sum over the 64 counts, which the first
-// wavefront of every workgroup takes for itself in six shuffle steps (it used to be a one-thread kernel between the two).
-__global__ __launch_bounds__(256)
-void ragged_scatter_kernel(const uint64_t *__restrict__ off, size_t n, unsigned *__restrict__ work,
-                           uint32_t *__restrict__ order)
+void ragged_order_kernel(const uint64_t *__restrict__ off, size_t n, unsigned *__restrict__ work, uint32_t *__restrict__ order,
+                         const unsigned phase)
 {
     __shared__ unsigned cnt[64], base[64], start[64];
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (phase == 0) {
+        if (threadIdx.x < 64) cnt[threadIdx.x] = 0;
+        __syncthreads();
+        if (i < n) atomicAdd(&cnt[ragged_bucket(off[i + 1] - off[i])], 1u);
+        __syncthreads();
+        if (threadIdx.x < 64 && cnt[threadIdx.x]) atomicAdd(&work[threadIdx.x], cnt[threadIdx.x]);
+        return;
+    }
     if (threadIdx.x < 64) {
         const unsigned b = threadIdx.x, own = work[b];
         unsigned acc = own;                                               // -> own + every bucket above b
@@ -818,7 +819,6 @@ void ragged_scatter_kernel(const uint64_t *__restrict__ off, size_t n, unsigned 
         cnt[b] = 0;
     }
     __syncthreads();
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned b = 0, rank = 0;
     if (i < n) { b = ragged_bucket(off[i + 1] - off[i]); rank = atomicAdd(&cnt[b], 1u); }
     __syncthreads();
@@ -840,8 +840,8 @@ err_t ragged_launch_order(const uint64_t *off, size_t n, hipStream_t st, const u
     uint32_t *order = (uint32_t *)(work + 128);
     B2H_TRY(hipMemsetAsync(work, 0, 128 * 4, st));
     const dim3 gn((unsigned)((n + 255) / 256)), tn(256);
-    hipLaunchKernelGGL(ragged_hist_kernel, gn, tn, 0, st, off, n, work);
-    hipLaunchKernelGGL(ragged_scatter_kernel, gn, tn, 0, st, off, n, work, order);
+    hipLaunchKernelGGL(ragged_order_kernel, gn, tn, 0, st, off, n, work, order, 0u);
+    hipLaunchKernelGGL(ragged_order_kernel, gn, tn, 0, st, off, n, work, order, 1u);
     *ord = order;
     return ERR_OK;
 }

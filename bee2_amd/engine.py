@@ -18,8 +18,12 @@ ERR_BAD_INPUT = 109
 ERR_OUTOFMEMORY = 110
 ERR_NOT_IMPLEMENTED = 119
 ERR_BAD_OID = 301
+ERR_BAD_FORMAT = 306
 ERR_BAD_PARAMS = 502
+ERR_BAD_SECKEY = 503
+ERR_BAD_PRIVKEY = 504
 ERR_BAD_PUBKEY = 505
+ERR_BAD_SHAREKEY = 508
 ERR_BAD_SIG = 510
 ERR_BAD_MAC = 511
 ERR_BAD_KEYTOKEN = 513
@@ -103,6 +107,8 @@ BATCH_SYMBOLS = [
     "bee2hip_beltAE_wrap_ragged", "bee2hip_beltAE_unwrap_ragged", "bee2hip_beltAE_ragged_stream",
     "bee2hip_beltFMT_batch", "bee2hip_beltFMT_batch_stream",
     "bee2hip_beltKWP_wrap_batch", "bee2hip_beltKWP_unwrap_batch", "bee2hip_beltKWP_batch_stream",
+    "bee2hip_beltKWP_wrap_keyed_batch", "bee2hip_beltKWP_unwrap_keyed_batch", "bee2hip_beltKWP_keyed_batch_stream",
+    "bee2hip_bpkiUnwrap_batch", "bee2hip_bpkiWrap_batch",
     "bee2hip_beltHMAC_ragged", "bee2hip_beltHMAC_verify_ragged", "bee2hip_beltHMAC_ragged_stream",
     "bee2hip_beltPBKDF2_batch", "bee2hip_beltPBKDF2_batch_stream",
     "bee2hip_set_device", "bee2hip_sync", "bee2hip_last_error", "bee2hip_version", "bee2hip_path_policy", "bee2hip_path_count",
@@ -409,6 +415,12 @@ class Engine:
             ctypes.c_int(unwrap), bytes(key), _sz(len(key)), self._optr(hdrs), self._optr(src), _sz(count), _sz(n),
             self._optr(dst), self._optr(codes), self._stream()), "beltKWP_batch_stream")
 
+    def beltKWP_keyed_batch_stream(self, unwrap, keys, key_len, hdrs, src, count, n, dst, codes=None):
+        """as beltKWP_batch_stream with one key-encryption key per record: keys (u8, n * key_len) is a device tensor"""
+        self._check(self.lib.bee2hip_beltKWP_keyed_batch_stream(
+            ctypes.c_int(unwrap), self._optr(keys), _sz(key_len), self._optr(hdrs), self._optr(src), _sz(count), _sz(n),
+            self._optr(dst), self._optr(codes), self._stream()), "beltKWP_keyed_batch_stream")
+
     def beltHMAC_ragged_stream(self, verify, key, keys, key_offsets, data, offsets, order, n, macs, mac_len, codes=None):
         """belt-hmac over n ragged messages: key (bytes: one key for the batch) or keys / key_offsets (device tensors: one key per
         record), data (u8), offsets (int64, n + 1), order (int32, n, or None), macs (u8, n * mac_len: written, or compared when
@@ -593,6 +605,54 @@ class Engine:
         code = self.lib.bee2hip_beltKWP_unwrap_batch(bytes(key), _sz(len(key)), None if hdrs is None else bytes(hdrs), bytes(tokens),
                                                      _sz(count), _sz(n), dst, codes)
         return code, dst.raw[:n * (count - 16)], list(codes)[:n]
+
+    def beltKWP_wrap_keyed_batch(self, keys, key_len, hdrs, records, count):
+        """belt-kwp under one key per record: keys = n * key_len octets -> (code, n * (count + 16) octets of tokens)"""
+        n = len(records) // count
+        assert len(records) == count * n and len(keys) == key_len * n and (hdrs is None or len(hdrs) == 16 * n)
+        dst = ctypes.create_string_buffer(max(1, n * (count + 16)))
+        code = self.lib.bee2hip_beltKWP_wrap_keyed_batch(bytes(keys), _sz(key_len), None if hdrs is None else bytes(hdrs),
+                                                         bytes(records), _sz(count), _sz(n), dst)
+        return code, dst.raw[:n * (count + 16)]
+
+    def beltKWP_unwrap_keyed_batch(self, keys, key_len, hdrs, tokens, count):
+        """tokens = n * count octets -> (code, n * (count - 16) octets, [ERR_OK / ERR_BAD_KEYTOKEN per record])"""
+        n = len(tokens) // count
+        assert len(tokens) == count * n and len(keys) == key_len * n and (hdrs is None or len(hdrs) == 16 * n)
+        dst, codes = ctypes.create_string_buffer(max(1, n * (count - 16))), (_u32 * max(n, 1))()
+        code = self.lib.bee2hip_beltKWP_unwrap_keyed_batch(bytes(keys), _sz(key_len), None if hdrs is None else bytes(hdrs),
+                                                           bytes(tokens), _sz(count), _sz(n), dst, codes)
+        return code, dst.raw[:n * (count - 16)], list(codes)[:n]
+
+    def bpkiUnwrap_batch(self, kind, epkis, pwds):
+        """kind 0: bpkiPrivkeyUnwrap, 1: bpkiShareUnwrap of every container with its password
+        -> (code, [key or b"" per record], [code per record], the raw n * 64 octets)"""
+        n = len(epkis)
+        assert len(pwds) == n
+        edata, eoffs, _ = self._pack(epkis)
+        pdata, poffs, _ = self._pack(pwds)
+        keys, lens, codes = ctypes.create_string_buffer(max(1, 64 * n)), (_u32 * max(n, 1))(), (_u32 * max(n, 1))()
+        code = self.lib.bee2hip_bpkiUnwrap_batch(ctypes.c_int(kind), edata, eoffs, pdata, poffs, _sz(n), keys, lens, codes)
+        raw = keys.raw[:64 * n]
+        return code, [raw[64 * i:64 * i + lens[i]] for i in range(n)], list(codes)[:n], raw
+
+    def bpkiWrap_batch(self, kind, keys, pwds, salts, iters, length_only=False):
+        """kind 0: bpkiPrivkeyWrap, 1: bpkiShareWrap; keys = a list of n keys of one length, salts = n strings of 8 octets
+        -> (code, [container per record]), or with length_only (code, the length of one container)"""
+        n = len(keys)
+        key_len = len(keys[0]) if keys else 0
+        assert len(pwds) == n and len(salts) == n and all(len(k) == key_len for k in keys) and all(len(x) == 8 for x in salts)
+        pdata, poffs, _ = self._pack(pwds)
+        length = _sz(0)
+        f = self.lib.bee2hip_bpkiWrap_batch
+        code = f(ctypes.c_int(kind), b"".join(bytes(k) for k in keys), _sz(key_len), pdata, poffs, b"".join(bytes(x) for x in salts),
+                 _sz(iters), _sz(n), None, ctypes.byref(length))
+        if code != ERR_OK or length_only:
+            return code, length.value
+        out = ctypes.create_string_buffer(max(1, n * length.value))
+        code = f(ctypes.c_int(kind), b"".join(bytes(k) for k in keys), _sz(key_len), pdata, poffs, b"".join(bytes(x) for x in salts),
+                 _sz(iters), _sz(n), out, ctypes.byref(length))
+        return code, [out.raw[length.value * i:length.value * (i + 1)] for i in range(n)]
 
     def _hmac_keys(self, key):
         """one key for the batch (bytes) or one per record (a list) -> (key, key_len, keys, key_offsets)"""

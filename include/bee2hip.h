@@ -68,9 +68,12 @@ typedef uint32_t err_t;
 #define ERR_FILE_NOT_FOUND    ((err_t)202)   /* err.h:105 */
 #define ERR_BAD_OID          ((err_t)301)   /* err.h:132 */
 #define ERR_BAD_RNG          ((err_t)304)   /* err.h:138 */
+#define ERR_BAD_FORMAT       ((err_t)306)   /* err.h:142 */
 #define ERR_BAD_PARAMS       ((err_t)502)   /* err.h:180 */
+#define ERR_BAD_SECKEY       ((err_t)503)   /* err.h:182 */
 #define ERR_BAD_PRIVKEY      ((err_t)504)   /* err.h:184 */
 #define ERR_BAD_PUBKEY       ((err_t)505)   /* err.h:186 */
+#define ERR_BAD_SHAREKEY     ((err_t)508)   /* err.h:192 */
 #define ERR_BAD_SIG          ((err_t)510)   /* err.h:196 */
 #define ERR_BAD_MAC          ((err_t)511)   /* err.h:198 */
 #define ERR_BAD_KEYTOKEN     ((err_t)513)   /* err.h */
@@ -459,6 +462,22 @@ err_t bee2hip_beltKWP_unwrap_batch(const octet key[], size_t key_len, const octe
 err_t bee2hip_beltKWP_batch_stream(int unwrap, const octet key[], size_t key_len, const void *d_hdrs, const void *d_src,
                                    size_t count, size_t n, void *d_dst, void *d_codes, void *stream);
 
+/* The same with ONE KEY-ENCRYPTION KEY PER RECORD: record i is
+       beltKWPWrap / beltKWPUnwrap(dst_i, src_i, count, hdr_i, keys + i * key_len, key_len)   (belt_kwp.c:19-50, :52-91),
+   key_len = 16, 24 or 32 for the whole batch.  Tokens wrapped under per-record keys are what key transport and the containers
+   below produce.  The same kernel text serves in a second instantiation (belt_kwp_batch_kernel<true>; the shared-key code
+   is unchanged): the keys are a launch argument, each read by its record's lane once before the rounds, octet by octet, and
+   expanded as beltKeyExpand2 does.  Contract, limits, codes and overlap rules are those of the three entries above, with
+   these differences: keys == NULL with n > 0 is ERR_BAD_INPUT; in the stream form d_keys is a
+   DEVICE pointer (n * key_len octets, no alignment) that must not meet d_dst -- an overlap of the two ranges is ERR_BAD_INPUT
+   with nothing written.  The host forms stage the keys with the records and zero that staging when the call ends. */
+err_t bee2hip_beltKWP_wrap_keyed_batch(const octet *keys, size_t key_len, const octet *hdrs, const octet *src, size_t count,
+                                       size_t n, octet *dst);
+err_t bee2hip_beltKWP_unwrap_keyed_batch(const octet *keys, size_t key_len, const octet *hdrs, const octet *src, size_t count,
+                                         size_t n, octet *dst, err_t *codes);
+err_t bee2hip_beltKWP_keyed_batch_stream(int unwrap, const void *d_keys, size_t key_len, const void *d_hdrs, const void *d_src,
+                                         size_t count, size_t n, void *d_dst, void *d_codes, void *stream);
+
 /* ---- belt-hmac and belt-pbkdf2 over n records (STB 34.101.31; belt.h, src/crypto/belt/belt_hmac.c, belt_pbkdf.c) -------
    Record by record these are bee2's one-shots
        beltHMAC(mac_i, msg_i, len_i, key_i, key_len_i)  and  beltPBKDF2(key_i, pwd_i, pwd_len_i, iter, salt_i, salt_len).
@@ -504,6 +523,37 @@ err_t bee2hip_beltPBKDF2_batch_stream(const void *d_pwds, const void *d_pwd_offs
    the host.  bee2's step functions of belt-hmac are not exported. */
 err_t beltHMAC(octet mac[32], const void *src, size_t count, const octet key[], size_t len);
 err_t beltPBKDF2(octet key[32], const octet pwd[], size_t pwd_len, size_t iter, const octet salt[], size_t salt_len);
+
+/* ---- bpki password-protected containers, n in one call (STB 34.101.78; bpki.h, src/crypto/bpki.c:206-548) -------------
+   kind = 0: a bign private key of 24, 32, 48 or 64 octets (bpkiPrivkeyWrap / bpkiPrivkeyUnwrap, bpki.c:313-425);
+   kind = 1: a bels share of 17, 25 or 33 octets (bpkiShareWrap / bpkiShareUnwrap, bpki.c:433-548); any other kind is
+   ERR_BAD_INPUT.  A container is beltPBKDF2(pwd, iter, salt[8]) -> belt-kwp of the PrivateKeyInfo frame under that key with a
+   zero header, inside the EncryptedPrivateKeyInfo frame.  The frames are parsed and built on the host with bee2's DER
+   strictness (bee2_amd/csrc/bpki_der.hpp); the passwords are stretched by belt_hmac_batch_kernel, one launch per distinct
+   iteration count, and the derived keys stay on the device as the per-record keys of belt_kwp_batch_kernel, one launch per
+   distinct pair (iteration count, token length) -- one in all for a batch from one issuer, at most 64 under the limits below, each
+   a few microseconds next to PBKDF2; they are zeroed there before the call returns.  bee2's own bpki* names are not exported.
+   Unwrap: record i is the container epkis[epki_offsets[i] .. epki_offsets[i+1]) with the password
+   pwds[pwd_offsets[i] .. pwd_offsets[i+1]).  codes[i] is the code bee2 returns for it, in bee2's order (bpki.c:374-425):
+   ERR_BAD_FORMAT (outer frame), ERR_BAD_INPUT (iter = 0, or encData below 32 octets), ERR_BAD_KEYTOKEN (wrong password),
+   ERR_BAD_FORMAT (inner frame), for a share ERR_BAD_SHAREKEY (first octet outside 1 .. 16).  An accepted record has its key
+   at keys + 64 i, zeros behind it up to 64 octets, and its length in key_lens[i]; a refused one 64 zero octets and length 0.
+   DIFFERENCES FROM bee2: codes[i] = ERR_NOT_IMPLEMENTED, with nothing computed, for iter above 2^17 (the count comes from an
+   untrusted container and a launch holds the GPU for a time proportional to it) and for encData above 1024 octets; more than
+   8 distinct iteration counts or more than 8 distinct encData lengths among the records that reach the device make the whole
+   call ERR_NOT_IMPLEMENTED with nothing written.  The call returns ERR_OK when it ran; when no record reaches the device (or
+   n = 0) it does so without a device.
+   Wrap: all n records share key_len and iter; record i has the key keys + i * key_len, its password and the salt salts + 8 i.
+   *epki_len (may be NULL) receives the length of one container, which (kind, key_len, iter) fix; epkis == NULL returns that
+   length only, as bee2; else container i is written at epkis + i * *epki_len, octet for octet what bee2 writes.  iter below
+   10000 is ERR_BAD_INPUT, a key_len that is none of the kind's ERR_BAD_PRIVKEY (kind 0) or ERR_BAD_SECKEY (kind 1), iter above
+   2^17 ERR_NOT_IMPLEMENTED, a share whose first octet is outside 1 .. 16 ERR_BAD_SECKEY for the whole call with nothing written
+   (also when epkis == NULL and keys is given, as bpki.c:445-447; a length query with keys == NULL looks at no share).
+   Both: ERR_BAD_INPUT for n >= 2^32, decreasing offsets, or a needed pointer that is NULL. */
+err_t bee2hip_bpkiUnwrap_batch(int kind, const octet *epkis, const uint64_t *epki_offsets, const octet *pwds,
+                               const uint64_t *pwd_offsets, size_t n, octet *keys, uint32_t *key_lens, err_t *codes);
+err_t bee2hip_bpkiWrap_batch(int kind, const octet *keys, size_t key_len, const octet *pwds, const uint64_t *pwd_offsets,
+                             const octet *salts, size_t iter, size_t n, octet *epkis, size_t *epki_len);
 
 /* ---- one host batch over several GPUs from one process --------------------------------
    The batch is cut into contiguous index ranges (bee2hip_multi_plan), one worker thread per device runs the
